@@ -118,6 +118,31 @@ def dump_engine(e):
     return {"state": e.get_state(), "solver": e.get_solver_state(), "x": e.sim_get_state()[0]}
 
 
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: all files of all ranks together (.npy headers included)
+
+
+def dump_outputs(e, out_dir, first_index, budget, suffix=""):
+    """--dump-outputs: what the timed path (mpcq_sim_steps) computed in its last period, as its caller reads it back -- plant states
+    and controls, the solver's iterate (predicted states and inputs, the previous prediction), the RGP posterior, the per-instance
+    status and tracking accumulators -- one float64 DIR/<name><suffix>.npy per array, rows = quadrotors.  Beyond `budget` bytes a
+    fixed seeded sample of the quadrotors (the same rows in every file; quad_index = their global indices).  Returns a summary."""
+    x, w = e.sim_get_state()
+    st = e.get_state()
+    arrays = {"plant_state": x, "control": w, "pred_states": st["X"], "pred_inputs": st["U"], "pred_prev": st["x_pred_prev"],
+              "rgp_mu": st["mu"], "rgp_C": st["C"], "status": e.get_status(), "tracking_stats": e.get_solver_state()["stats"]}
+    B = x.shape[0]
+    per_quad = 8 * (1 + sum(a[0].size for a in arrays.values()))        # (+1: quad_index)
+    keep = int(min(B, max(1, (budget - 256 * (len(arrays) + 1)) // per_quad)))
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    arrays = {k: a[rows] for k, a in arrays.items()}
+    arrays["quad_index"] = first_index + rows
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": sorted(f"{k}{suffix}.npy" for k in arrays), "quads": keep, "of": B, "dtype": "float64",
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, f"{k}{suffix}.npy")) for k in arrays)}
+
+
 def parity_on_workload(dump, refs, N, nb, device, quads=64, periods=30, free_running=False, precision=PRECISION_F64, lib_path=None):
     """Oracle parity ON THE BENCH WORKLOAD (the checker, never the thing measured): a sample of `quads` quadrotors of a
     pre-rolled engine (`dump` = dump_engine of it, `refs` its references) -- every quadrotor whose last solve went through
@@ -468,6 +493,10 @@ def main():
                     help="exit non-zero when WORLD_SIZE > 1 and the RCCL reduction did not run (the default under WORLD_SIZE > 1)")
     ap.add_argument("--no-strict-rccl", dest="strict_rccl", action="store_false",
                     help="accept a reduction over the host group when RCCL cannot be brought up (the line says which one ran)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed in their last step (plant states, controls, predicted trajectory, "
+                         "RGP posterior, status, tracking accumulators) as DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded "
+                         "sample of the quadrotors beyond that); under WORLD_SIZE > 1 every rank writes DIR/<name>_rank<r>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -540,6 +569,9 @@ def main():
     kmin, kmax = e.get_kernel_time_minmax()
     its = e.get_qp_iter()
     status = e.get_status()
+    dumped = None
+    if args.dump_outputs:      # the engine as the timed steps left it (read back outside the timed region, before any further leg)
+        dumped = dump_outputs(e, args.dump_outputs, rank * B, DUMP_BYTES // world, f"_rank{rank}" if world > 1 else "")
     if dist is not None:
         import torch
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -661,6 +693,8 @@ def main():
             "tracking": {"rms_pos_m": float(np.sqrt(stats[0] / (3 * max(stats[2], 1)))), "steps": float(stats[2]),
                          "max_pos_err_m": float(np.sqrt(stats[3])), "failed_instances": float(stats[4])},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if steady is not None:
             out["steady_state"] = steady
             # machine-readable form of "which number is representative": `value` is the driver's short window, whose launches hold more or

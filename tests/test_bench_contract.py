@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,3 +118,74 @@ def test_eight_ranks_reduce_both_statistics_through_the_rccl_branch():
     assert len(sw["per_rank"]["ranks"]) == 8 and 0 < sw["efficiency_vs_best_rank"] <= 1.0 + 1e-9
     assert sw["tracking_steps"] == 16 * (2 + 5 + 20)              # every rank's (pre-roll + warm-up + timed) periods arrived in the sum
     assert d["tracking"]["steps"] == 8 * (2 + 1 + 2)
+
+
+def _dump_run(tmp, name, steps, warmup):
+    d = os.path.join(tmp, name)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "tests", "run_bench_emu.py"), "--steps", str(steps), "--warmup", str(warmup),
+                                   "--preroll", "3", "--batch", "2", "--horizon", "5", "--nb", "10", "--no-cpu-baseline", "--no-alt", "--no-parity",
+                                   "--steady", "0", "--dump-outputs", d], cwd=ROOT)
+    lines = [ln for ln in out.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = _check(lines[0], 1)
+    assert line["steps"] == steps and line["dump_outputs"]["quads"] == 2 and line["dump_outputs"]["bytes"] <= 64 * 10**6
+    files = sorted(os.listdir(d))
+    assert files == line["dump_outputs"]["files"]
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+
+
+def test_dump_outputs_are_reproducible_and_end_at_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays the timed path left behind, float64, bit for bit the same from run to run with the same
+    arguments; the same periods split differently between warm-up and timed steps end in the same state, one timed step more does not."""
+    a = _dump_run(str(tmp_path), "a", 2, 1)
+    assert a["plant_state"].shape == (2, 13) and a["control"].shape == (2, 4) and a["pred_states"].shape == (2, 6, 13)
+    assert a["pred_inputs"].shape == (2, 5, 4) and a["rgp_C"].shape == (2, 3, 10, 10) and np.array_equal(a["quad_index"], [0, 1])
+    assert all(v.dtype == np.float64 for v in a.values()) and np.isfinite(a["plant_state"]).all()
+    b = _dump_run(str(tmp_path), "b", 2, 1)
+    c = _dump_run(str(tmp_path), "c", 1, 2)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        assert np.array_equal(a[k], c[k]), k
+    d = _dump_run(str(tmp_path), "d", 3, 1)
+    assert not np.array_equal(a["plant_state"], d["plant_state"])
+
+
+def test_dump_outputs_sample_stays_within_64_mb(tmp_path):
+    """The largest BASELINE shape (8192 quadrotors, N = 50, 50 basis points) is ~0.5 GB of outputs: a fixed seeded sample of the
+    quadrotors, the same rows in every file, under 64 MB in all (a stand-in engine: no device needed)."""
+    import bench
+
+    class Stub:
+        def __init__(self, B, N, nb):
+            self.B, self.N, self.nb = B, N, nb
+            self.base = np.arange(B, dtype=np.float64)
+
+        def sim_get_state(self):
+            return np.repeat(self.base[:, None], 13, 1), np.repeat(self.base[:, None], 4, 1)
+
+        def get_state(self):
+            B, N, nb = self.B, self.N, self.nb
+            col = lambda *s: np.broadcast_to(self.base.reshape((B,) + (1,) * len(s)), (B,) + s).copy()
+            return dict(X=col(N + 1, 13), U=col(N, 4), mu=col(3, nb), C=col(3, nb, nb), x_pred_prev=col(13),
+                        has_prev=np.ones(B, np.int32), idx=np.zeros(B, np.int32))
+
+        def get_status(self):
+            return self.base.astype(np.int32)
+
+        def get_solver_state(self):
+            return {"stats": np.repeat(self.base[:, None], 4, 1)}
+
+    r = bench.dump_outputs(Stub(8192, 50, 50), str(tmp_path / "big"), 8192, bench.DUMP_BYTES)
+    assert r["bytes"] <= 64 * 10**6 and 0 < r["quads"] < 8192
+    assert sum(os.path.getsize(tmp_path / "big" / f) for f in os.listdir(tmp_path / "big")) == r["bytes"]
+    idx = np.load(tmp_path / "big" / "quad_index.npy")
+    assert len(idx) == r["quads"] and (np.diff(idx) > 0).all()
+    for f in r["files"]:
+        a = np.load(tmp_path / "big" / f)
+        assert a.dtype == np.float64 and len(a) == r["quads"]
+        if f != "quad_index.npy":
+            assert np.array_equal(a.reshape(len(a), -1)[:, 0], idx - 8192), f     # every file holds the rows of the same quadrotors
+    bench.dump_outputs(Stub(8192, 50, 50), str(tmp_path / "again"), 8192, bench.DUMP_BYTES)
+    assert np.array_equal(np.load(tmp_path / "again" / "quad_index.npy"), idx)  # a fixed sample
+    small = bench.dump_outputs(Stub(1024, 20, 10), str(tmp_path / "small"), 0, bench.DUMP_BYTES)
+    assert small["quads"] == 1024                                                # the default workload is written whole
