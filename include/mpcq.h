@@ -144,8 +144,9 @@ typedef struct mpcq_config {
 typedef struct mpcq_engine mpcq_engine;
 
 const char* mpcq_last_error(void);
-/* "mpcq <major.minor> (gfx950, source <16 hex digits>)": the digits are the hash of the sources and the build recipe the library was
- * built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash. */
+/* "mpcq <major.minor[.patch]> (gfx950, source <16 hex digits>+<8 hex digits>)": the 16 digits are the hash of the sources and the build
+ * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
+ * The 8 behind them (since 0.6.1) hash the device generator of mpcq_replan (csrc/mpcq_replan.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -312,6 +313,37 @@ int mpcq_set_state(mpcq_engine* e, const double* X, const double* U, const doubl
  * finished flags [B].  With mpcq_get_state + mpcq_sim_get_state a restored engine continues bit for bit. */
 int mpcq_get_solver_state(mpcq_engine* e, int32_t* qp_iter, double* stats, int32_t* finished);
 int mpcq_set_solver_state(mpcq_engine* e, const int32_t* qp_iter, const double* stats, const int32_t* finished);
+
+/* ---- continuous operation (since 0.6.1): a finished flight is followed by the next one, planned from where the quadrotor stands
+ * (src/mpc_controller_node.py:372-399 -> request_trajectory :430-453 -> trajectory_received_cb :511-552), for the selected quadrotors
+ * only while the others keep flying.  Per-quadrotor result codes of mpcq_replan, out[b]: */
+#define MPCQ_REPLAN_DONE 0          /* new flight installed */
+#define MPCQ_REPLAN_SKIPPED 1       /* not selected */
+#define MPCQ_REPLAN_BAD_INPUT (-1)  /* non-finite start or waypoint */
+#define MPCQ_REPLAN_SINGULAR (-2)   /* as mpcq_traj.h -2 (reserved: like mpcq_minsnap_generate_order, the bisection counts a singular
+                                       solve as a limit violation, so such a flight ends in MPCQ_REPLAN_LIMITS) */
+#define MPCQ_REPLAN_LIMITS (-3)     /* as mpcq_traj.h -3: the limits cannot be met */
+#define MPCQ_REPLAN_TOO_LONG (-4)   /* the sampled flight has more rows than the Tmax of mpcq_set_trajectories */
+/* Minimum-snap flights planned and sampled on the device, one wavefront per selected quadrotor: for the vertices
+ * [start_b, wp[b,0], ..., wp[b,n_wp-1]] exactly the host generator's result, mpcq_minsnap_generate_order(.., v_max, a_max,
+ * derivative_to_optimize, ..) sampled like mpcq_minsnap_sample(.., dt) (positions / velocities may differ by one quantum of the
+ * 6-decimal rounding).  Selected: mask[b] != 0, or with mask == NULL the quadrotors whose finished flag is set on the device.
+ * start [B,3]; NULL: the position of the on-device plant (mpcq_sim_get_state; MPCQ_ERR_STATE without an earlier mpcq_sim_reset).
+ * On MPCQ_REPLAN_DONE the slot gets the new rows (padded with the last one up to Tmax), len[b] = the row count, the cursor goes to
+ * 0 and the finished flag to 0; nothing else of the quadrotor changes (iterate, RGP, x_pred_prev, has_prev, QP status, tracking
+ * accumulators).  A negative code leaves trajectory, cursor and finished flag as they were.  Waypoints of unselected quadrotors are
+ * not read for validity.  MPCQ_ERR_INVALID: n_wp outside 1..7, v_max / a_max / dt not > 0, derivative_to_optimize outside 2..4,
+ * wp NULL; MPCQ_ERR_STATE before mpcq_set_trajectories.  out [B] may be NULL. */
+int mpcq_replan(mpcq_engine* e, const double* start /*[B,3] or NULL*/, const double* wp /*[B,n_wp,3]*/, int32_t n_wp,
+                double v_max, double a_max, int32_t derivative_to_optimize, double dt,
+                const int32_t* mask /*[B] or NULL*/, int32_t* out /*[B] or NULL*/);
+/* The same slot install for host-made rows (the reference's 'circle' / 'line' requests): quadrotors idx[0..count), rows
+ * traj [count, Tmax, 13] of which the first len[j] are used; 1 <= len <= Tmax, indices in range and unique. */
+int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx /*[count]*/, int32_t count,
+                              const double* traj /*[count,Tmax,13]*/, const int32_t* len /*[count]*/);
+/* The trajectory buffer and lengths as they are now.  A checkpoint after replans restores with mpcq_set_trajectories(traj, len),
+ * then mpcq_set_state(idx = ...) and mpcq_set_solver_state(finished = ...). */
+int mpcq_get_trajectories(mpcq_engine* e, double* traj /*[B,Tmax,13] or NULL*/, int32_t* len /*[B] or NULL*/);
 
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)

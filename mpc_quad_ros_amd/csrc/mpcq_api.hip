@@ -19,6 +19,7 @@
 #endif
 #include "../../include/mpcq.h"
 #include "mpcq_kernels.hpp"
+#include "mpcq_replan.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -161,6 +162,11 @@ bool spd_inverse(const std::vector<double>& A, int n, std::vector<double>& Ai) {
 }  // namespace
 
 // ------------------------------------------------------------------ engine
+// What the trajectory-slot entry points (mpcq_replan, mpcq_replace_trajectories, mpcq_get_trajectories) work on: precision-independent
+// device arrays of the engine (trajectories, cursors and the plant state are float64 in every precision).
+struct TrajSlots {
+  double* traj; int* len; int* idx; int* finished; const double* plant; int Tmax;
+};
 struct mpcq_engine {
   virtual ~mpcq_engine() {}
   mpcq_config cfg;
@@ -179,6 +185,11 @@ struct mpcq_engine {
   std::vector<hipEvent_t> kev;   // per-launch event pairs of the last sim_steps call
   double ktime = 0, kmin = 0, kmax = 0;   // HIP-event time of the timed step-kernel launches: total, fastest, slowest
   int klaunches = 0;
+  bool have_sim = false;         // mpcq_sim_reset has set the plant state
+  // staging of mpcq_replan / mpcq_replace_trajectories (allocated on first use, grown when needed; freed by EngineT)
+  double *d_rp_in = nullptr; size_t rp_in_elems = 0;   // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
+  int* d_rp_int = nullptr;                             // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
+  virtual TrajSlots traj_slots() = 0;
   virtual int init() = 0;
   virtual int reset() = 0;
   virtual int set_trajectories(const double*, const int32_t*, int32_t) = 0;
@@ -242,7 +253,8 @@ struct EngineT : mpcq_engine {
   ~EngineT() override {
     DeviceGuard guard(cfg.device);
     void* ptrs[] = {st.qp_work, st.chk, st.finished, d_cmd, st.stage, st.X, st.U, st.mu, st.C, st.xpp, st.yref, st.yrefN, st.w, st.xpred, st.cost, st.stats, st.has_prev, st.idx,
-                    st.status, st.qp_iter, d_basis, d_Kxinv, d_Kx, d_xin, d_uin, d_tmp, d_traj, d_xs, d_vb, d_ad, d_tlen, d_stats5, d_order};
+                    st.status, st.qp_iter, d_basis, d_Kxinv, d_Kx, d_xin, d_uin, d_tmp, d_traj, d_xs, d_vb, d_ad, d_tlen, d_stats5, d_order,
+                    d_rp_in, d_rp_int};
     for (void* p : ptrs)
       if (p) (void)hipFree(p);
     if (h_pin) (void)hipHostFree(h_pin);
@@ -256,6 +268,7 @@ struct EngineT : mpcq_engine {
     if (comm && !comm_borrowed && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
   }
 
+  TrajSlots traj_slots() override { return TrajSlots{d_traj, d_tlen, st.idx, st.finished, d_xs, m.Tmax}; }
   template <typename P> int dalloc(P*& p, size_t n) {
     HIP_TRY(hipMalloc((void**)&p, (n ? n : 1) * sizeof(*p)));
     HIP_TRY(hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(*p), stream));
@@ -915,9 +928,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.1 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.1 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1011,7 +1024,12 @@ void* mpcq_stream(mpcq_engine* e) { return e ? (void*)e->stream : nullptr; }
 int mpcq_get_command(mpcq_engine* e, double* rotor, double* coll, double* rates) { ENTER(e); return e->get_command(rotor, coll, rates); }
 int mpcq_get_finished(mpcq_engine* e, int32_t* o) { ENTER(e); if (!o) return fail(MPCQ_ERR_INVALID, "null argument"); return e->get_finished(o); }
 int mpcq_get_reference_chunk(mpcq_engine* e, double* o) { ENTER(e); if (!o) return fail(MPCQ_ERR_INVALID, "null argument"); return e->get_chunk(o); }
-int mpcq_sim_reset(mpcq_engine* e, const double* x0) { ENTER(e); return e->sim_reset(x0); }
+int mpcq_sim_reset(mpcq_engine* e, const double* x0) {
+  ENTER(e);
+  const int rc = e->sim_reset(x0);
+  if (!rc) e->have_sim = true;
+  return rc;
+}
 int mpcq_sim_steps(mpcq_engine* e, int32_t K, int32_t n_sub, double sim_dt) { ENTER(e); return e->sim_steps(K, n_sub, sim_dt); }
 int mpcq_sim_run(mpcq_engine* e, int32_t K, int32_t n_sub, double sim_dt) { ENTER(e); return e->sim_run(K, n_sub, sim_dt); }
 // `while control_time < optimization_dt: quad.update(w, simulation_dt); control_time += simulation_dt`
@@ -1107,5 +1125,80 @@ int mpcq_get_state(mpcq_engine* e, double* X, double* U, double* mu, double* C, 
 int mpcq_set_state(mpcq_engine* e, const double* X, const double* U, const double* mu, const double* C, const double* xpp, const int32_t* hp, const int32_t* idx) { ENTER(e); return e->set_state(X, U, mu, C, xpp, hp, idx); }
 int mpcq_get_solver_state(mpcq_engine* e, int32_t* qp_iter, double* stats4, int32_t* finished) { ENTER(e); return e->get_solver_state(qp_iter, stats4, finished); }
 int mpcq_set_solver_state(mpcq_engine* e, const int32_t* qp_iter, const double* stats4, const int32_t* finished) { ENTER(e); return e->set_solver_state(qp_iter, stats4, finished); }
+
+// ---- continuous operation: trajectory slots (mpcq_replan.hpp)
+namespace {
+int rp_staging(mpcq_engine* e, size_t in_elems) {
+  if (e->rp_in_elems < in_elems) {
+    if (e->d_rp_in) { (void)hipFree(e->d_rp_in); e->d_rp_in = nullptr; e->rp_in_elems = 0; }
+    HIP_TRY(hipMalloc((void**)&e->d_rp_in, in_elems * sizeof(double)));
+    e->rp_in_elems = in_elems;
+  }
+  if (!e->d_rp_int) HIP_TRY(hipMalloc((void**)&e->d_rp_int, (size_t)3 * e->B * sizeof(int)));
+  return 0;
+}
+}  // namespace
+
+int mpcq_replan(mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize,
+                double dt, const int32_t* mask, int32_t* out) {
+  ENTER(e);
+  if (!wp) return fail(MPCQ_ERR_INVALID, "mpcq_replan: null waypoints");
+  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, "mpcq_replan: n_wp outside 1..7");
+  if (!(v_max > 0) || !(a_max > 0) || !(dt > 0)) return fail(MPCQ_ERR_INVALID, "mpcq_replan: v_max, a_max and dt must be > 0");
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, "mpcq_replan: derivative_to_optimize outside 2..4");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replan needs mpcq_set_trajectories first");
+  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, "mpcq_replan without start points needs mpcq_sim_reset first (the plant state)");
+  const size_t B = e->B, nwp = B * n_wp * 3;
+  int rc;
+  if ((rc = rp_staging(e, nwp + B * 3))) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_rp_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (start) HIP_TRY(hipMemcpyAsync(e->d_rp_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(e->d_rp_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  int* d_code = e->d_rp_int + B;
+  hipLaunchKernelGGL(mpcq::replan::replan_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
+                     start ? (const double*)(e->d_rp_in + nwp) : t.plant, start ? 3 : 13, (const double*)e->d_rp_in, (int)n_wp, v_max, a_max,
+                     (int)derivative_to_optimize, dt, mask ? (const int*)e->d_rp_int : nullptr, d_code);
+  HIP_TRY(hipGetLastError());
+  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count, const double* traj, const int32_t* len) {
+  ENTER(e);
+  if (!idx || !traj || !len) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: null argument");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replace_trajectories needs mpcq_set_trajectories first");
+  if (count < 0 || count > e->B) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: count outside 0..B");
+  std::vector<char> seen(e->B, 0);
+  for (int j = 0; j < count; ++j) {
+    if (idx[j] < 0 || idx[j] >= e->B) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: index out of range");
+    if (seen[idx[j]]++) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: duplicate index");
+    if (len[j] < 1 || len[j] > t.Tmax) return fail(MPCQ_ERR_INVALID, "trajectory length out of range");
+  }
+  if (count == 0) return 0;
+  const size_t rows = (size_t)count * t.Tmax * 13;
+  int rc;
+  if ((rc = rp_staging(e, rows))) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_rp_in, traj, rows * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_rp_int, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_rp_int + e->B, len, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(mpcq::replan::install_kernel, dim3(count), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
+                     (const double*)e->d_rp_in, (const int*)e->d_rp_int, (const int*)(e->d_rp_int + e->B));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int mpcq_get_trajectories(mpcq_engine* e, double* traj, int32_t* len) {
+  ENTER(e);
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_get_trajectories needs mpcq_set_trajectories first");
+  if (traj) HIP_TRY(hipMemcpyAsync(traj, t.traj, (size_t)e->B * t.Tmax * 13 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (len) HIP_TRY(hipMemcpyAsync(len, t.len, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
 
 }  // extern "C"

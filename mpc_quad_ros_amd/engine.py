@@ -42,6 +42,8 @@ def order_bin(it):
 
 WARM_BUDGET, WARM_PINS, WARM_WRONG, WARM_BOUNCE, WARM_NUMERIC, WARM_SKIPPED = 1, 2, 3, 4, 5, 6
 SOLVE_LOW_ACCURACY = 8
+# per-quadrotor result codes of Engine.replan (include/mpcq.h MPCQ_REPLAN_*)
+REPLAN_DONE, REPLAN_SKIPPED, REPLAN_BAD_INPUT, REPLAN_SINGULAR, REPLAN_LIMITS, REPLAN_TOO_LONG = 0, 1, -1, -2, -3, -4
 
 
 class Engine:
@@ -88,6 +90,41 @@ class Engine:
             lengths = np.full(self.B, traj.shape[1])
         lengths = np.ascontiguousarray(lengths, dtype=np.int32)
         self._check(self.lib.mpcq_set_trajectories(self.h, _lib.d(traj), _lib.i(lengths), traj.shape[1]))
+        self._tmax = traj.shape[1]
+
+    # ---- continuous operation: replace the flights of some quadrotors while the others keep flying
+    def replan(self, wp, v_max, a_max, dt=0.01, derivative_to_optimize=4, start=None, mask=None):
+        """Minimum-snap flights planned on the device from start [B,3] (None: the on-device plant's position) through wp [B,n_wp,3]
+        for the selected quadrotors (mask [B] != 0; None: those whose finished flag is set), installed in their slots with the
+        cursor at 0.  Returns the per-quadrotor codes [B] (REPLAN_*)."""
+        wp = self._f(wp)
+        if wp.ndim != 3 or wp.shape[0] != self.B or wp.shape[2] != 3:
+            raise ValueError(f"wp must be [B={self.B}, n_wp, 3]")
+        start = self._f(start, (self.B, 3))
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        out = np.zeros(self.B, np.int32)
+        self._check(self.lib.mpcq_replan(self.h, _lib.d(start), _lib.d(wp), wp.shape[1], float(v_max), float(a_max),
+                                         int(derivative_to_optimize), float(dt), _lib.i(mask), _lib.i(out)))
+        return out
+
+    def replace_trajectories(self, idx, traj, lengths):
+        """Host-made rows traj [count, Tmax, 13] (the first lengths[j] used) into the slots of quadrotors idx [count]."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        traj = self._f(traj)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        tmax = getattr(self, "_tmax", None)
+        if tmax is None or traj.shape != (len(idx), tmax, NX) or lengths.shape != idx.shape:
+            raise ValueError(f"traj must be [count={len(idx)}, Tmax={tmax}, 13] and lengths [count]")
+        self._check(self.lib.mpcq_replace_trajectories(self.h, _lib.i(idx), len(idx), _lib.d(traj), _lib.i(lengths)))
+
+    def get_trajectories(self):
+        """(traj [B, Tmax, 13], lengths [B]) as they are on the device now."""
+        tmax = getattr(self, "_tmax", None)
+        if tmax is None:
+            raise _lib.MpcqError("get_trajectories needs set_trajectories first")
+        traj, lengths = np.zeros((self.B, tmax, NX)), np.zeros(self.B, np.int32)
+        self._check(self.lib.mpcq_get_trajectories(self.h, _lib.d(traj), _lib.i(lengths)))
+        return traj, lengths
 
     def set_reference(self, yref, yrefN):
         yref = self._f(yref, (self.B, self.N, NY))

@@ -241,6 +241,13 @@ def minsnap_mission(seed: int, index: int, min_samples: int, v_max: float = 12.0
     return np.concatenate(rows)
 
 
+def flight_waypoints(seed: int, index: int, leg: int, num_waypoints: int = 3, **kw):
+    """The waypoints [num_waypoints, 3] (without the start) that minsnap_mission(seed, index, ...) draws for flight `leg`.  The draws
+    do not depend on the start point, so a flight planned on the device from where the quadrotor stands (Engine.replan) goes
+    through the same random waypoints as the pre-chained mission's."""
+    return random_waypoints([int(seed), 7919 * (int(leg) + 1)], index, num_waypoints=num_waypoints, **kw)[1:]
+
+
 def _mission_chunk(args):
     """Worker: missions of a contiguous index block, as float32-free compact rows (positions and velocities; the other
     columns of a reference are constants)."""
