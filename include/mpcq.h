@@ -22,6 +22,7 @@
 #define MPCQ_H
 
 #include <stdint.h>
+#include "mpcq_nl_options.h"   /* mpcq_minsnap_nl_options (mpcq_replan_nonlinear) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -146,7 +147,8 @@ typedef struct mpcq_engine mpcq_engine;
 const char* mpcq_last_error(void);
 /* "mpcq <major.minor[.patch]> (gfx950, source <16 hex digits>+<8 hex digits>)": the 16 digits are the hash of the sources and the build
  * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
- * The 8 behind them (since 0.6.1) hash the device generator of mpcq_replan (csrc/mpcq_replan.hpp). */
+ * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
+ * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -337,6 +339,18 @@ int mpcq_set_solver_state(mpcq_engine* e, const int32_t* qp_iter, const double* 
 int mpcq_replan(mpcq_engine* e, const double* start /*[B,3] or NULL*/, const double* wp /*[B,n_wp,3]*/, int32_t n_wp,
                 double v_max, double a_max, int32_t derivative_to_optimize, double dt,
                 const int32_t* mask /*[B] or NULL*/, int32_t* out /*[B] or NULL*/);
+/* Since 0.6.2.  mpcq_replan with the reference generator's nonlinear stage: for each selected quadrotor exactly the host library's
+ * mpcq_minsnap_nonlinear(.., v_max, a_max, derivative_to_optimize, opts, ..) -- segment times and free vertex derivatives optimised by
+ * Subplex from the linear stage, soft speed / acceleration limits -- sampled like mpcq_minsnap_sample(.., dt).  Selection, start, result
+ * codes and install as mpcq_replan (MPCQ_REPLAN_SINGULAR: the linear stage's system is singular; MPCQ_REPLAN_LIMITS: the linear stage
+ * lasts longer than 300 s, which mpcq_minsnap_nonlinear refuses too: segment times are bounded above by 10 x their start).  Soft limits: a flight may exceed
+ * v_max / a_max and is installed anyway; info reports its peaks.  opts NULL: the defaults.  Optional outputs (NaN rows for quadrotors
+ * without a result): info [B,6] = f at the start, f at the end, evaluations, total duration, peak speed, peak acceleration;
+ * pieces [B,n_wp,33]; d_free [B,n_wp-1,3,3].  MPCQ_ERR_INVALID as mpcq_replan, plus options outside the rules of include/mpcq_nl_options.h (time_penalty must be > 0). */
+int mpcq_replan_nonlinear(mpcq_engine* e, const double* start /*[B,3] or NULL*/, const double* wp /*[B,n_wp,3]*/, int32_t n_wp,
+                          double v_max, double a_max, int32_t derivative_to_optimize, double dt,
+                          const int32_t* mask /*[B] or NULL*/, int32_t* out /*[B] or NULL*/, const mpcq_minsnap_nl_options* opts /*or NULL*/,
+                          double* info /*[B,6] or NULL*/, double* pieces /*[B,n_wp,33] or NULL*/, double* d_free /*[B,n_wp-1,3,3] or NULL*/);
 /* The same slot install for host-made rows (the reference's 'circle' / 'line' requests): quadrotors idx[0..count), rows
  * traj [count, Tmax, 13] of which the first len[j] are used; 1 <= len <= Tmax, indices in range and unique. */
 int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx /*[count]*/, int32_t count,

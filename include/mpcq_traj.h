@@ -27,7 +27,7 @@ int mpcq_minsnap_solve(const double* wp, int32_t n, const double* T, double* pie
  * built with), 2 acceleration -- PolynomialOptimization<8>::solveLinear of mav_trajectory_generation */
 int mpcq_minsnap_solve_order(const double* wp, int32_t n, const double* T, int32_t derivative_to_optimize, double* pieces);
 /* the linear stage of the reference's generator as published: estimateSegmentTimes (Nfabian, constant 6.5) + solveLinear, no scaling onto
- * the limits (the binary's nonlinear stage, an early-stopped Subplex run, is not reproducible: DESIGN.md section 6.1) */
+ * the limits (the binary's nonlinear stage follows: mpcq_minsnap_nonlinear) */
 int mpcq_minsnap_linear(const double* wp, int32_t n, double v_max, double a_max, int32_t derivative_to_optimize, double* pieces);
 /* Since round 6.  Pieces (and cost) for GIVEN segment times and free vertex derivatives: the map the reference generator's nonlinear stage
  * (mav_trajectory_generation::PolynomialOptimizationNonLinear<8>, behind src/trajectory_generation/TrajectoryGenerator.py:177-191) evaluates
@@ -37,6 +37,7 @@ int mpcq_minsnap_linear(const double* wp, int32_t n, double v_max, double a_max,
  * same family (tests/test_minsnap.py). */
 int mpcq_minsnap_from_derivatives(const double* wp, int32_t n, const double* T, const double* d_free, int32_t derivative_to_optimize,
                                   double* pieces, double* cost);
+/* Since 0.6.2 the nonlinear stage of the reference's generator follows the linear one: include/mpcq_traj_nl.h (same library). */
 /* estimate + solve + uniform time scaling until the sampled peak speed / acceleration meet v_max / a_max */
 int mpcq_minsnap_generate(const double* wp, int32_t n, double v_max, double a_max, double* pieces);
 /* ... with the cost on derivative_to_optimize (mpcq_minsnap_generate = 4) */

@@ -14,6 +14,34 @@ _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
 
+
+class NlOptions(ctypes.Structure):
+    """mpcq_minsnap_nl_options (include/mpcq_nl_options.h): options of the min-snap generator's nonlinear stage."""
+    _fields_ = [("time_penalty", ctypes.c_double), ("soft_constraint_weight", ctypes.c_double), ("soft_constraint_cap", ctypes.c_double),
+                ("f_rel", ctypes.c_double), ("x_rel", ctypes.c_double), ("max_evaluations", ctypes.c_int32), ("time_cost", ctypes.c_int32),
+                ("use_soft_constraints", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def nl_defaults():
+    """The defaults as the host library states them (mpcq_minsnap_nl_defaults = MPCQ_MINSNAP_NL_DEFAULTS), as a dict."""
+    from .trajectories import _traj_lib
+    d = _traj_lib().mpcq_minsnap_nl_defaults()
+    return {name: getattr(d, name) for name, _ in NlOptions._fields_ if name != "reserved"}
+
+
+def nl_options(opts=None):
+    """NlOptions from a dict of overrides of the defaults (None: NULL, i.e. the library's defaults)."""
+    if opts is None:
+        return None
+    base = nl_defaults()
+    unknown = set(opts) - set(base)
+    if unknown:
+        raise ValueError(f"unknown nonlinear-stage options {sorted(unknown)}")
+    return NlOptions(**{**base, **opts}, reserved=0)
+
+
+_np = ctypes.POINTER(NlOptions)
+
 # every symbol declared in include/mpcq.h: (name, restype, argtypes)
 SYMBOLS = [
     ("mpcq_last_error", ctypes.c_char_p, []),
@@ -65,6 +93,8 @@ SYMBOLS = [
     ("mpcq_get_solver_state", ctypes.c_int, [_vp, _ip, _dp, _ip]),
     ("mpcq_set_solver_state", ctypes.c_int, [_vp, _ip, _dp, _ip]),
     ("mpcq_replan", ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, _ip, _ip]),
+    ("mpcq_replan_nonlinear", ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, _ip,
+                                             _ip, _np, _dp, _dp, _dp]),
     ("mpcq_replace_trajectories", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _dp, _ip]),
     ("mpcq_get_trajectories", ctypes.c_int, [_vp, _dp, _ip]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),

@@ -12,8 +12,10 @@
 // the 6-decimal rounding of the samples), through the waypoints and C^3 to what the "%.6f" coefficients of its CSV allow -- i.e.
 // points of the family (segment times T, free vertex derivatives d_P) of mpcq_minsnap_from_derivatives below, which reproduces them
 // to that rounding; their d_P are NOT the optimum of the linear stage at their own T (off by up to 40 % of the velocity scale): the
-// binary's nonlinear stage moved times AND derivatives (an early-stopped Subplex run over both).  So this generator is the same
-// trajectory FAMILY, not the same trajectories.
+// binary's nonlinear stage moved times AND derivatives (an early-stopped Subplex run over both).  That stage is built here since 0.6.2
+// (mpcq_minsnap_nonlinear: the same objective -- jerk cost, time penalty, soft speed / acceleration limits -- and a Subplex written from
+// its description, in mpcq_minsnap_nl.hpp); what stays unreproducible is nlopt's exact iterate path, so these are flights of the same
+// formulation, not the logged flights themselves.
 //
 // The unconstrained formulation: with d = (p, v, a, j) at both ends of a segment, coefficients c = A(T)^-1 d and cost
 // c' Q(T) c, so the total cost is a quadratic form in the vertex derivatives; the free ones (v, a, j at interior waypoints)
@@ -24,6 +26,10 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
+
+#include "../../include/mpcq_traj.h"
+#include "../../include/mpcq_traj_nl.h"
+#include "mpcq_minsnap_nl.hpp"
 
 namespace {
 
@@ -257,8 +263,8 @@ int mpcq_minsnap_from_derivatives(const double* wp, int32_t n, const double* T, 
 // The LINEAR stage of the reference's generator, as published: segment times from estimateSegmentTimes(vertices, v_max, a_max) =
 // estimateSegmentTimesNfabian with its constant 6.5 (mpcq_minsnap_estimate_times), then the linear solve for derivative_to_optimize.
 // The binary continues from exactly this point with nlopt's Subplex over times and free derivatives, stopped early at loose
-// tolerances -- that part is not reproducible; this part is, and tests/test_minsnap.py documents how far it
-// is from the logged references per waypoint file.  No scaling onto the limits: peak speed / acceleration are what they are.
+// tolerances -- mpcq_minsnap_nonlinear below restates that stage (nlopt's exact iterate path is what stays
+// unreproducible); tests/test_minsnap.py documents how far this linear stage is from the logged references per waypoint file.  No scaling onto the limits: peak speed / acceleration are what they are.
 int mpcq_minsnap_linear(const double* wp, int32_t n, double v_max, double a_max, int32_t derivative_to_optimize, double* pieces) {
   if (n < 2) return -1;
   std::vector<double> T(n - 1);
@@ -295,6 +301,113 @@ int mpcq_minsnap_generate_order(const double* wp, int32_t n, double v_max, doubl
       if (violation(mid) > 1.0) lo = mid; else hi = mid;
     }
   return violation(hi) <= 1.0 ? 0 : -3;
+}
+
+// ---- the nonlinear stage (mpcq_minsnap_nl.hpp; the device restatement is mpcq_replan_nl.hpp)
+}  // extern "C"
+namespace {
+
+struct NlProblem {
+  double V[mpcq_nl::MAXV][3];
+  int n, order;
+  double v_max, a_max;
+  mpcq_nl::Opts o;
+  double A1i[NC][NC], M1[NC][NC];
+  // per evaluation
+  double Tp[mpcq_nl::MAXS][15], coef[mpcq_nl::MAXS][3][NC], q[mpcq_nl::MAXS][3];
+  int first[mpcq_nl::MAXV], steps[mpcq_nl::MAXS];
+  double vpk, apk;
+};
+
+bool nl_setup(NlProblem& P, const double* wp, int n, double v_max, double a_max, int order, const mpcq_minsnap_nl_options* opts) {
+  if (!wp || n < 2 || n > mpcq_nl::MAXV || !(v_max > 0) || !(a_max > 0) || !std::isfinite(v_max) || !std::isfinite(a_max) || order < 2 || order > 4) return false;
+  P.o = mpcq_nl::nl_opts_from(opts);
+  if (!mpcq_nl::nl_opts_valid(P.o)) return false;
+  for (int v = 0; v < n; ++v)
+    for (int k = 0; k < 3; ++k) {
+      P.V[v][k] = wp[v * 3 + k];
+      if (!std::isfinite(P.V[v][k])) return false;
+    }
+  P.n = n; P.order = order; P.v_max = v_max; P.a_max = a_max;
+  mpcq_nl::nl_unit_forms(order, P.A1i, P.M1);
+  return true;
+}
+
+// f at x = [T, d_free]: the device's evaluation (mpcq_replan_nl.hpp nl_evaluate) with its lanes taken in order
+double nl_eval(NlProblem& P, const double* x, double* parts) {
+  const int ns = P.n - 1;
+  for (int s = 0; s < ns; ++s)
+    for (int k = -7; k <= 7; ++k) P.Tp[s][k + 7] = mpcq_nl::nl_ipow(x[s], k);
+  mpcq_nl::nl_grid(x, ns, P.first, P.steps);
+  for (int s = 0; s < ns; ++s)
+    for (int ax = 0; ax < 3; ++ax) {
+      double d[8];
+      mpcq_nl::nl_seg_d(P.V, P.n, x, s, ax, d);
+      mpcq_nl::nl_seg_coef_cost(P.A1i, P.M1, P.Tp[s], d, P.order, P.coef[s][ax], &P.q[s][ax]);
+    }
+  double vm = 0, am = 0;
+  for (int s = 0; s < ns; ++s)
+    for (int k = 0; k <= P.steps[s]; ++k) {
+      double sv, sa;
+      mpcq_nl::nl_sample_peak(P.coef[s], x[s], k, P.steps[s], &sv, &sa);
+      vm = vm < sv ? sv : vm;
+      am = am < sa ? sa : am;
+    }
+  P.vpk = vm; P.apk = am;
+  return mpcq_nl::nl_total(P.q, ns, x, P.o, vm, am, P.v_max, P.a_max, parts);
+}
+
+}  // namespace
+extern "C" {
+
+mpcq_minsnap_nl_options mpcq_minsnap_nl_defaults(void) {
+  const mpcq_minsnap_nl_options o = MPCQ_MINSNAP_NL_DEFAULTS;
+  return o;
+}
+
+double mpcq_minsnap_nl_objective(const double* wp, int32_t n, const double* T, const double* d_free, double v_max, double a_max,
+                                 int32_t derivative_to_optimize, const mpcq_minsnap_nl_options* opts, double* parts) {
+  NlProblem P;
+  if (!T || (n > 2 && !d_free) || !nl_setup(P, wp, n, v_max, a_max, derivative_to_optimize, opts)) return NAN;
+  const int m = n - 1, nv = m + 9 * (n - 2);
+  double x[mpcq_nl::NV];
+  for (int i = 0; i < nv; ++i) x[i] = i < m ? T[i] : d_free[i - m];
+  for (int s = 0; s < m; ++s)
+    if (!(T[s] > 0) || !(T[s] <= mpcq_nl::T_MAX)) return NAN;
+  return nl_eval(P, x, parts);
+}
+
+// The optimiser: the linear stage's start, then Subplex (mpcq_nl::sbx_next) on nl_eval until it stops; the pieces of its best point.
+int mpcq_minsnap_nonlinear(const double* wp, int32_t n, double v_max, double a_max, int32_t derivative_to_optimize, const mpcq_minsnap_nl_options* opts,
+                           double* pieces, double* d_free_out, double* info) {
+  NlProblem P;
+  if (!pieces || !nl_setup(P, wp, n, v_max, a_max, derivative_to_optimize, opts)) return -1;
+  const int m = n - 1, nv = m + 9 * (n - 2);
+  double x0[mpcq_nl::NV], lo[mpcq_nl::NV], hi[mpcq_nl::NV], step[mpcq_nl::NV], R[mpcq_nl::MAXF][mpcq_nl::RW];
+  double total0 = 0;
+  for (int s = 0; s < m; ++s) total0 = total0 + (x0[s] = mpcq_nl::nl_estimate_time(P.V, s, v_max, a_max));
+  if (!(total0 <= mpcq_nl::MAX_START_DURATION)) return -3;
+  if (!mpcq_nl::nl_linear_dfree(P.V, n, x0, P.M1, derivative_to_optimize, R, x0 + m)) return -2;
+  mpcq_nl::nl_box(n, v_max, a_max, x0, lo, hi, step);
+  mpcq_nl::Sbx S;
+  mpcq_nl::sbx_init(S, nv, x0, step, lo, hi, P.o.f_rel, P.o.x_rel, P.o.max_evaluations);
+  double f = 0;
+  while (mpcq_nl::sbx_next(S, f)) f = nl_eval(P, S.xt, nullptr);
+  nl_eval(P, S.x, nullptr);   // the pieces and peaks of the result (not counted)
+  for (int s = 0; s < m; ++s) {
+    pieces[(size_t)s * 33] = S.x[s];
+    for (int ax = 0; ax < 3; ++ax)
+      for (int i = 0; i < NC; ++i) pieces[(size_t)s * 33 + 1 + ax * NC + i] = P.coef[s][ax][i];
+    for (int i = 0; i < NC; ++i) pieces[(size_t)s * 33 + 25 + i] = 0.0;
+  }
+  if (d_free_out)
+    for (int i = m; i < nv; ++i) d_free_out[i - m] = S.x[i];
+  if (info) {
+    double tot = 0;
+    for (int s = 0; s < m; ++s) tot += S.x[s];
+    info[0] = S.f0; info[1] = S.f; info[2] = S.nev; info[3] = tot; info[4] = P.vpk; info[5] = P.apk;
+  }
+  return 0;
 }
 
 // Sampling of the pieces into the 13-state reference, the chain save_evals_csv -> load_trajectory of the reference

@@ -20,6 +20,7 @@
 #include "../../include/mpcq.h"
 #include "mpcq_kernels.hpp"
 #include "mpcq_replan.hpp"
+#include "mpcq_replan_nl.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -928,9 +929,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.1 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.2 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.1 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.2 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1161,6 +1162,42 @@ int mpcq_replan(mpcq_engine* e, const double* start, const double* wp, int32_t n
                      (int)derivative_to_optimize, dt, mask ? (const int*)e->d_rp_int : nullptr, d_code);
   HIP_TRY(hipGetLastError());
   if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int mpcq_replan_nonlinear(mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize,
+                          double dt, const int32_t* mask, int32_t* out, const mpcq_minsnap_nl_options* opts, double* info, double* pieces, double* d_free) {
+  ENTER(e);
+  if (!wp) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: null waypoints");
+  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: n_wp outside 1..7");
+  if (!(v_max > 0) || !(a_max > 0) || !(dt > 0) || !std::isfinite(v_max) || !std::isfinite(a_max))
+    return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: v_max, a_max and dt must be finite and > 0");
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: derivative_to_optimize outside 2..4");
+  const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
+  if (!mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: options out of range");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replan_nonlinear needs mpcq_set_trajectories first");
+  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, "mpcq_replan_nonlinear without start points needs mpcq_sim_reset first (the plant state)");
+  const size_t B = e->B, nwp = B * n_wp * 3, n_info = B * 6, n_pc = B * n_wp * 33, n_df = B * (n_wp - 1) * 9;
+  int rc;
+  if ((rc = rp_staging(e, nwp + B * 3 + n_info + n_pc + n_df))) return rc;
+  double* d_info = e->d_rp_in + nwp + B * 3;
+  double* d_pc = d_info + n_info;
+  double* d_df = d_pc + n_pc;
+  HIP_TRY(hipMemcpyAsync(e->d_rp_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (start) HIP_TRY(hipMemcpyAsync(e->d_rp_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(e->d_rp_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  int* d_code = e->d_rp_int + B;
+  hipLaunchKernelGGL(mpcq::replan::replan_nl_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::NlLds), e->stream, t.traj, t.Tmax, t.len, t.idx,
+                     t.finished, start ? (const double*)(e->d_rp_in + nwp) : t.plant, start ? 3 : 13, (const double*)e->d_rp_in, (int)n_wp, v_max,
+                     a_max, (int)derivative_to_optimize, dt, mask ? (const int*)e->d_rp_int : nullptr, d_code, o, info ? d_info : nullptr,
+                     pieces ? d_pc : nullptr, d_free && n_df ? d_df : nullptr);
+  HIP_TRY(hipGetLastError());
+  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (info) HIP_TRY(hipMemcpyAsync(info, d_info, n_info * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (pieces) HIP_TRY(hipMemcpyAsync(pieces, d_pc, n_pc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (d_free && n_df) HIP_TRY(hipMemcpyAsync(d_free, d_df, n_df * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }

@@ -42,7 +42,9 @@ __device__ inline double ipow(double t, int k) {   // t^k for |k| <= 7
   return k < 0 ? 1.0 / r : r;
 }
 
-// A(1)^-1 by the host's elimination (one lane), M(1) for `order` (lanes over (a, b))
+// A(1)^-1 by the host's elimination (one lane), M(1) for `order` (lanes over (a, b)).
+// Also the start of mpcq_replan_nonlinear: mpcq_minsnap_nl.hpp nl_unit_forms restates it operation for operation for the host library,
+// and host / device bit parity depends on the two staying identical (tests/test_replan_nonlinear.py) -- change both together.
 __device__ inline void unit_forms(Lds& S, int order) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x;
@@ -90,7 +92,9 @@ __device__ inline void unit_forms(Lds& S, int order) {
   __syncthreads();
 }
 
-// pieces at the scaled times S.T: coefficients into S.coef; false if the system is singular (wave-uniform)
+// pieces at the scaled times S.T: coefficients into S.coef; false if the system is singular (wave-uniform).
+// Also the start of mpcq_replan_nonlinear: mpcq_minsnap_nl.hpp nl_linear_dfree restates the assembly, elimination and back substitution
+// operation for operation for the host library -- change both together (bit parity: tests/test_replan_nonlinear.py).
 __device__ inline bool solve_pieces(Lds& S, int n, int order) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x, ns = n - 1, nf = 3 * (n - 2);

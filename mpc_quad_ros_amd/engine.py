@@ -107,6 +107,27 @@ class Engine:
                                          int(derivative_to_optimize), float(dt), _lib.i(mask), _lib.i(out)))
         return out
 
+    def replan_nonlinear(self, wp, v_max, a_max, dt=0.01, derivative_to_optimize=3, start=None, mask=None, opts=None, return_pieces=False):
+        """replan with the reference generator's nonlinear stage (mpcq_replan_nonlinear): segment times and free vertex derivatives
+        optimised by Subplex under soft speed / acceleration limits, exactly the host library's mpcq_minsnap_nonlinear.  opts: dict of
+        overrides of the defaults (_lib.nl_defaults()).  Returns (codes [B], info [B,6]: f start, f end, evaluations, duration, peak
+        speed, peak acceleration -- NaN rows where no flight was made); with return_pieces also pieces [B,n_wp,33] and
+        d_free [B,n_wp-1,3,3]."""
+        wp = self._f(wp)
+        if wp.ndim != 3 or wp.shape[0] != self.B or wp.shape[2] != 3:
+            raise ValueError(f"wp must be [B={self.B}, n_wp, 3]")
+        start = self._f(start, (self.B, 3))
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        o = _lib.nl_options(opts)
+        out, info = np.zeros(self.B, np.int32), np.zeros((self.B, 6))
+        n_wp = wp.shape[1]
+        pieces = np.zeros((self.B, n_wp, 33)) if return_pieces else None
+        d_free = np.zeros((self.B, max(n_wp - 1, 0), 3, 3)) if return_pieces else None
+        self._check(self.lib.mpcq_replan_nonlinear(self.h, _lib.d(start), _lib.d(wp), n_wp, float(v_max), float(a_max),
+                                                   int(derivative_to_optimize), float(dt), _lib.i(mask), _lib.i(out),
+                                                   None if o is None else ctypes.byref(o), _lib.d(info), _lib.d(pieces), _lib.d(d_free)))
+        return (out, info, pieces, d_free) if return_pieces else (out, info)
+
     def replace_trajectories(self, idx, traj, lengths):
         """Host-made rows traj [count, Tmax, 13] (the first lengths[j] used) into the slots of quadrotors idx [count]."""
         idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)

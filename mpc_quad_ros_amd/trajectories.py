@@ -115,6 +115,12 @@ def _traj_lib():
         lib.mpcq_minsnap_generate_order.argtypes = [dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, dp]
         lib.mpcq_minsnap_from_derivatives.argtypes = [dp, ctypes.c_int32, dp, dp, ctypes.c_int32, dp, dp]
         lib.mpcq_minsnap_write_csv.argtypes = [ctypes.c_char_p, dp, ctypes.c_int32]
+        from . import _lib
+        npp = ctypes.POINTER(_lib.NlOptions)
+        lib.mpcq_minsnap_nl_objective.argtypes = [dp, ctypes.c_int32, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, npp, dp]
+        lib.mpcq_minsnap_nl_objective.restype = ctypes.c_double
+        lib.mpcq_minsnap_nonlinear.argtypes = [dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, npp, dp, dp, dp]
+        lib.mpcq_minsnap_nl_defaults.restype = _lib.NlOptions
         lib.mpcq_minsnap_sample.argtypes = [dp, ctypes.c_int32, ctypes.c_double, dp, ctypes.c_int32]
         _TRAJ_LIB = lib
     return _TRAJ_LIB
@@ -180,6 +186,43 @@ def reference_linear_stage(waypoints, v_max, a_max, derivative_to_optimize=3):
     if rc:
         raise ValueError(f"mpcq_minsnap_linear failed ({rc})")
     return pieces
+
+
+def _nl_opts_ref(opts):
+    import ctypes
+    from . import _lib
+    o = _lib.nl_options(opts)
+    return None if o is None else ctypes.byref(o)
+
+
+def minsnap_nl_objective(waypoints, times, d_free, v_max, a_max, derivative_to_optimize=3, opts=None):
+    """The nonlinear stage's objective (include/mpcq_traj_nl.h mpcq_minsnap_nl_objective) at times [n-1], d_free [n-2,3,3]:
+    (f, parts [4] = derivative cost, time cost, soft speed term, soft acceleration term).  opts: dict of overrides of the defaults."""
+    wp = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+    T = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    d = np.ascontiguousarray(d_free, dtype=np.float64).reshape(-1)
+    if T.shape != (len(wp) - 1,) or d.size != 9 * max(len(wp) - 2, 0):
+        raise ValueError("waypoints [n,3], times [n-1], d_free [n-2,3,3]")
+    parts = np.zeros(4)
+    f = _traj_lib().mpcq_minsnap_nl_objective(_dptr(wp), len(wp), _dptr(T), _dptr(d), float(v_max), float(a_max), int(derivative_to_optimize),
+                                              _nl_opts_ref(opts), _dptr(parts))
+    if not np.isfinite(f):
+        raise ValueError("mpcq_minsnap_nl_objective: bad arguments")
+    return f, parts
+
+
+def minsnap_pieces_nonlinear(waypoints, v_max, a_max, derivative_to_optimize=3, opts=None):
+    """The reference generator's nonlinear stage (include/mpcq_traj_nl.h mpcq_minsnap_nonlinear): segment times and free vertex derivatives
+    optimised by Subplex from the linear stage under soft limits.  Returns (pieces [n-1,33], d_free [n-2,3,3], info [6] = f start,
+    f end, evaluations, total duration, peak speed, peak acceleration).  2 <= n <= 8 waypoints."""
+    wp = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
+    n = len(wp)
+    pieces, d_free, info = np.zeros((max(n - 1, 0), 33)), np.zeros((max(n - 2, 0), 3, 3)), np.zeros(6)
+    rc = _traj_lib().mpcq_minsnap_nonlinear(_dptr(wp), n, float(v_max), float(a_max), int(derivative_to_optimize), _nl_opts_ref(opts),
+                                            _dptr(pieces), _dptr(d_free), _dptr(info))
+    if rc:
+        raise ValueError(f"mpcq_minsnap_nonlinear failed ({rc})")
+    return pieces, d_free, info
 
 
 def minsnap_pieces_order(waypoints, v_max, a_max, derivative_to_optimize):
