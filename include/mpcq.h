@@ -148,7 +148,7 @@ const char* mpcq_last_error(void);
 /* "mpcq <major.minor[.patch]> (gfx950, source <16 hex digits>+<8 hex digits>)": the 16 digits are the hash of the sources and the build
  * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
  * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
- * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp). */
+ * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp) and, since 0.6.3, the flight recorder (csrc/mpcq_record.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -255,7 +255,8 @@ int mpcq_sim_steps(mpcq_engine* e, int32_t K, int32_t n_sub, double sim_dt);
 /* The same K closed-loop iterations as ONE launch in which every instance runs through its K control periods
  * without waiting for the others (instances are independent; src/execute_trajectory.py:196-279 is a loop over ONE
  * quadrotor).  Same arithmetic, same results as mpcq_sim_steps; the per-period outputs readable afterwards
- * (mpcq_get_*, mpcq_sim_get_state) are those of the last period. */
+ * (mpcq_get_*, mpcq_sim_get_state) are those of the last period (per-period logs: the flight recorder with mpcq_sim_steps;
+ * MPCQ_ERR_STATE while a recording is active, see mpcq_record_start). */
 int mpcq_sim_run(mpcq_engine* e, int32_t K, int32_t n_sub, double sim_dt);
 /* The reference's plant loop between two solves (src/execute_trajectory.py:232-243):
  * `while control_time < optimization_dt: quad.update(w, simulation_dt); control_time += simulation_dt`.
@@ -358,6 +359,41 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx /*[count]*/, in
 /* The trajectory buffer and lengths as they are now.  A checkpoint after replans restores with mpcq_set_trajectories(traj, len),
  * then mpcq_set_state(idx = ...) and mpcq_set_solver_state(finished = ...). */
 int mpcq_get_trajectories(mpcq_engine* e, double* traj /*[B,Tmax,13] or NULL*/, int32_t* len /*[B] or NULL*/);
+
+/* ---- flight recorder (since 0.6.3): per-period logs of a swarm that flies on the device (the reference appends one row per control
+ * step, src/mpc_controller_node.py:353-364, src/execute_trajectory.py:269-275).  A period is one fused step of every quadrotor: one
+ * mpcq_step / mpcq_step_device_async call, one iteration of mpcq_sim_steps / mpcq_sim_control_periods.  Periods count from
+ * mpcq_record_start; period k is recorded when k % every == 0, one row per selected quadrotor, written on the device by a launch behind
+ * the step launch (and, with MPCQ_RECORD_DRAG, a launch in front of it); the host reads the buffers once.  Recording changes no
+ * result of the engine.  mpcq_solve is not a period.  mpcq_reset, mpcq_set_state, mpcq_set_trajectories and the replan calls are
+ * allowed during a recording and show in later rows.  mpcq_sim_run (one persistent launch) does not record: MPCQ_ERR_STATE while a
+ * recording is active.  Every value is stored as float64 (MPCQ_PRECISION_F32: mu and C converted as mpcq_get_rgp converts them).
+ * Fields (bit mask) and the width of one row: */
+#define MPCQ_RECORD_X_ODOM   1    /* [13] the measurement the step solved from (plant state at the period start / the caller's x_meas) */
+#define MPCQ_RECORD_X_REF    2    /* [13] row 0 of the reference chunk the step used (the node's x_ref; the row of the tracking statistic) */
+#define MPCQ_RECORD_W        4    /* [4]  the control of the step */
+#define MPCQ_RECORD_X_PRED   8    /* [13] the nominal prediction of the step */
+#define MPCQ_RECORD_COST    16    /* [1]  cost of the step */
+#define MPCQ_RECORD_DRAG    32    /* [6]  v_body(3), a_drag(3): compute_a_drag of the measurement against the x_pred_prev the step started from */
+#define MPCQ_RECORD_RGP_MU  64    /* [3*nb] RGP mean after the step (nb > 0 only) */
+#define MPCQ_RECORD_RGP_C  128    /* [3*nb*nb] RGP covariance after the step (nb > 0 only) */
+#define MPCQ_RECORD_SOLVER 256    /* [4] int32: status, qp_iter, trajectory cursor the step used, finished flag after the step */
+/* Starts a recording of quadrotors quads[0..count) (NULL: all B, count ignored), `capacity` rows per quadrotor.  A full buffer does not
+ * wrap: later recorded periods count as dropped (mpcq_record_clear empties it).  Memory: capacity x count x (sum of the widths) x 8 bytes.
+ * MPCQ_ERR_INVALID: count <= 0 with quads, an index out of range or twice, fields 0 or unknown bits, every < 1, capacity < 1, an RGP
+ * field with nb = 0.  MPCQ_ERR_STATE: a recording is active.  MPCQ_ERR_DEVICE: the buffers cannot be allocated. */
+int mpcq_record_start(mpcq_engine* e, const int32_t* quads /*[count] or NULL*/, int32_t count, int32_t fields, int32_t every, int32_t capacity);
+/* rows recorded, periods dropped (buffer full), periods counted since mpcq_record_start.  Any pointer may be NULL. */
+int mpcq_record_info(mpcq_engine* e, int32_t* rows, int64_t* dropped, int64_t* periods);
+/* One recorded double field (a single MPCQ_RECORD_* bit other than MPCQ_RECORD_SOLVER, else MPCQ_ERR_INVALID), out [count, rows, width]:
+ * quadrotors in the caller's order of mpcq_record_start, rows in time order. */
+int mpcq_record_get(mpcq_engine* e, int32_t field, double* out);
+int mpcq_record_get_solver(mpcq_engine* e, int32_t* out /*[count, rows, 4]*/);
+int mpcq_record_get_periods(mpcq_engine* e, int64_t* out /*[rows]: the period number of each row*/);
+/* rows = 0 and dropped = 0; the selection, the fields and the period count stay */
+int mpcq_record_clear(mpcq_engine* e);
+/* frees the buffers; recording off.  get / info / clear / stop without an active recording: MPCQ_ERR_STATE. */
+int mpcq_record_stop(mpcq_engine* e);
 
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)

@@ -12,6 +12,7 @@ DEFAULT_LIB = os.path.join(_HERE, "libmpcq.so")
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
+_lp = ctypes.POINTER(ctypes.c_int64)
 _vp = ctypes.c_void_p
 
 
@@ -97,6 +98,13 @@ SYMBOLS = [
                                              _ip, _np, _dp, _dp, _dp]),
     ("mpcq_replace_trajectories", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _dp, _ip]),
     ("mpcq_get_trajectories", ctypes.c_int, [_vp, _dp, _ip]),
+    ("mpcq_record_start", ctypes.c_int, [_vp, _ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("mpcq_record_info", ctypes.c_int, [_vp, _ip, _lp, _lp]),
+    ("mpcq_record_get", ctypes.c_int, [_vp, ctypes.c_int32, _dp]),
+    ("mpcq_record_get_solver", ctypes.c_int, [_vp, _ip]),
+    ("mpcq_record_get_periods", ctypes.c_int, [_vp, _lp]),
+    ("mpcq_record_clear", ctypes.c_int, [_vp]),
+    ("mpcq_record_stop", ctypes.c_int, [_vp]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),
     ("mpcq_learn_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mpcq_learn_destroy", ctypes.c_int, [_vp]),
@@ -135,3 +143,7 @@ def d(a):
 
 def i(a):
     return None if a is None else a.ctypes.data_as(_ip)
+
+
+def l(a):
+    return None if a is None else a.ctypes.data_as(_lp)

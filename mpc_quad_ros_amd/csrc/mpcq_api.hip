@@ -21,6 +21,7 @@
 #include "mpcq_kernels.hpp"
 #include "mpcq_replan.hpp"
 #include "mpcq_replan_nl.hpp"
+#include "mpcq_record.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -168,6 +169,26 @@ bool spd_inverse(const std::vector<double>& A, int n, std::vector<double>& Ai) {
 struct TrajSlots {
   double* traj; int* len; int* idx; int* finished; const double* plant; int Tmax;
 };
+// The flight recorder (mpcq_record_*): host bookkeeping and device buffers of a recording; the launches are EngineT's (rec_snapshot,
+// rec_write).  The selection is kept sorted (a group of mpcq_sim_steps covers a contiguous part of it); pos maps the caller's order to it.
+struct Recorder {
+  bool on = false;
+  int fields = 0, every = 1, capacity = 0, count = 0, rows = 0;
+  long long dropped = 0, periods = 0;
+  std::vector<int> sorted, pos;          // selection ascending; pos[j] = place of the caller's j-th quadrotor in `sorted`
+  std::vector<int> glo, ghi;             // part of `sorted` inside group g of mpcq_sim_steps: [glo[g], ghi[g])
+  std::vector<long long> period_of;      // period number of every row
+  int* d_sel = nullptr;                  // sorted selection
+  double* d_f[mpcq::record::NF - 1] = {};   // double fields, [capacity][count][width]
+  int* d_solver = nullptr;               // [capacity][count][4]
+  double* d_snap = nullptr;              // [count][SNAP]: x_pred_prev and has_prev in front of the step (MPCQ_RECORD_DRAG)
+  void release() {
+    void* ptrs[] = {d_sel, d_solver, d_snap};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (double* p : d_f) if (p) (void)hipFree(p);
+    *this = Recorder();
+  }
+};
 struct mpcq_engine {
   virtual ~mpcq_engine() {}
   mpcq_config cfg;
@@ -190,6 +211,7 @@ struct mpcq_engine {
   // staging of mpcq_replan / mpcq_replace_trajectories (allocated on first use, grown when needed; freed by EngineT)
   double *d_rp_in = nullptr; size_t rp_in_elems = 0;   // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
   int* d_rp_int = nullptr;                             // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
+  Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
   virtual TrajSlots traj_slots() = 0;
   virtual int init() = 0;
   virtual int reset() = 0;
@@ -259,6 +281,7 @@ struct EngineT : mpcq_engine {
     for (void* p : ptrs)
       if (p) (void)hipFree(p);
     if (h_pin) (void)hipHostFree(h_pin);
+    rec.release();
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     for (hipEvent_t ev : kev) (void)hipEventDestroy(ev);
@@ -602,6 +625,43 @@ struct EngineT : mpcq_engine {
     return 0;
   }
   int base_mode() const { return (cfg.flags & MPCQ_FLAG_STATIC_GP) ? mpcq::MODE_STATIC_GP : 0; }
+  // ---- flight recorder (mpcq_record.hpp).  A period (one fused step of every quadrotor) counts whether it is recorded or not; the row a
+  // recorded one writes (-1: not recorded -- not its turn, or the buffer is full and the period counts as dropped)
+  int rec_next_row() {
+    const long long p = rec.periods++;
+    if (p % rec.every) return -1;
+    if (rec.rows >= rec.capacity) { ++rec.dropped; return -1; }
+    rec.period_of.push_back(p);
+    return rec.rows++;
+  }
+  // in front of the step launch: what compute_a_drag of the step compares against (the post phase overwrites it), selection part [j0, j1)
+  void rec_snapshot(hipStream_t s, int j0, int j1) {
+    const int n = j1 - j0;
+    if (!(rec.fields & MPCQ_RECORD_DRAG) || n <= 0) return;
+    hipLaunchKernelGGL(mpcq::record::record_snapshot_kernel, dim3((n * mpcq::record::SNAP + 63) / 64), dim3(64), 0, s, (const int*)rec.d_sel, j0, n,
+                       (const double*)st.xpp, (const int*)st.has_prev, rec.d_snap);
+  }
+  // behind the step launch, in front of any plant launch: row `row` of every recorded field for the selection part [j0, j1)
+  void rec_write(hipStream_t s, int j0, int j1, int row, const double* xmeas) {
+    const int n = j1 - j0;
+    if (n <= 0) return;
+    mpcq::record::Args<T> a;
+    std::memset(&a, 0, sizeof(a));
+    a.sel = rec.d_sel; a.j0 = j0; a.n = n; a.count = rec.count; a.row = row;
+    long blocks = 0;
+    for (int f = 0; f < mpcq::record::NF; ++f) {
+      a.blk[f] = (int)blocks;
+      if (rec.fields >> f & 1) blocks += ((long)n * mpcq::record::width(f, nb) + 63) / 64;
+    }
+    a.blk[mpcq::record::NF] = (int)blocks;
+    for (int f = 0; f < mpcq::record::NF - 1; ++f) a.out[f] = rec.d_f[f];
+    a.solver = rec.d_solver; a.snap = rec.d_snap;
+    a.xmeas = xmeas; a.w = st.w; a.xpred = st.xpred; a.cost = st.cost; a.traj = st.traj;
+    a.tlen = st.tlen; a.idx = st.idx; a.finished = st.finished; a.status = st.status; a.qp_iter = st.qp_iter;
+    a.mu = st.mu; a.C = st.C;
+    a.Tmax = m.Tmax; a.N = N; a.skip = m.skip; a.nb = nb; a.dt_pred = m.dt_pred;
+    hipLaunchKernelGGL(mpcq::record::record_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+  }
   // one lockstep period of the quadrotors [b0, b0 + nq) on stream `strm`; ev_begin (if any) is recorded in front of the STEP kernel, behind
   // the ordering launch, so that the event pairs of sim_steps time the step kernel alone
   void launch_period(const mpcq::DevState<T>& s, int mode, hipEvent_t ev_begin = nullptr, hipStream_t strm = nullptr, int b0 = 0, int nq = -1) {
@@ -688,7 +748,10 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemcpyAsync(d_xin, h_pin, nx * sizeof(double), hipMemcpyHostToDevice, stream));
     st.x_meas = d_xin;
     int rc;
+    const int row = rec.on ? rec_next_row() : -1;
+    if (row >= 0) rec_snapshot(stream, 0, rec.count);
     if ((rc = launch_step(mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode()))) return rc;
+    if (row >= 0) rec_write(stream, 0, rec.count, row, d_xin);
     HIP_TRY(hipMemcpyAsync(h_pin + nx, st.w, nw * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (x_pred_out) HIP_TRY(hipMemcpyAsync(h_pin + nx + nw, st.xpred, nx * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -701,10 +764,13 @@ struct EngineT : mpcq_engine {
     mpcq::DevState<T> s2 = st;   // measurement and control are float64 in every precision (DevState::x_meas / w)
     s2.x_meas = d_x;
     s2.w_ext = d_w;   // the engine's own control record st.w is written as well (mpcq_get_command, mpcq_sim_plant_period(w = NULL))
+    const int row = rec.on ? rec_next_row() : -1;
+    if (row >= 0) rec_snapshot(stream, 0, rec.count);
     HIP_TRY(hipEventRecord(ev0, stream));
     launch_period(s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, stream));
+    if (row >= 0) rec_write(stream, 0, rec.count, row, d_x);
     timed = true;
     return chk_after();   // (synchronises in the checked build only)
   }
@@ -734,17 +800,21 @@ struct EngineT : mpcq_engine {
       HIP_TRY(hipEventRecord(gstart, stream));
       for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(gstreams[g], gstart, 0));
       const int per = ((B + G - 1) / G + 7) / 8 * 8;   // quadrotors per group (the last one takes what is left)
-      for (int k = 0; k < K; ++k)
+      for (int k = 0; k < K; ++k) {
+        const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of group g cover the selection inside [g0, g1))
         for (int g = 0; g < G; ++g) {
           const int g0 = g * per, g1 = std::min(B, g0 + per);
           if (g0 >= g1) continue;
           const bool timed_launch = g == 0 && k % stride == 0;
           const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
+          if (row >= 0) rec_snapshot(gstreams[g], rec.glo[g], rec.ghi[g]);
           launch_period(s2, mode, timed_launch ? kev[2 * (k / stride)] : nullptr, gstreams[g], g0, g1 - g0);
           if (timed_launch) HIP_TRY(hipEventRecord(kev[2 * (k / stride) + 1], gstreams[g]));
+          if (row >= 0) rec_write(gstreams[g], rec.glo[g], rec.ghi[g], row, d_xs);
           if (split || k == K - 1)
             hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g1 - g0 + 63) / 64), dim3(64), 0, gstreams[g], m, d_xs + (size_t)g0 * 13, st.w + (size_t)g0 * 4, n_sub, sim_dt, g1 - g0);
         }
+      }
       for (int g = 1; g < G; ++g) {
         HIP_TRY(hipEventRecord(gdone[g], gstreams[g]));
         HIP_TRY(hipStreamWaitEvent(stream, gdone[g], 0));
@@ -753,8 +823,11 @@ struct EngineT : mpcq_engine {
     for (int k = 0; k < K; ++k) {
       const bool timed_launch = k % stride == 0;
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
+      const int row = rec.on ? rec_next_row() : -1;
+      if (row >= 0) rec_snapshot(stream, 0, rec.count);
       launch_period(s2, mode, timed_launch ? kev[2 * (k / stride)] : nullptr);
       if (timed_launch) HIP_TRY(hipEventRecord(kev[2 * (k / stride) + 1], stream));
+      if (row >= 0) rec_write(stream, 0, rec.count, row, d_xs);
       if (split || k == K - 1)
         hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, stream, m, d_xs, st.w, n_sub, sim_dt, B);
     }
@@ -775,6 +848,7 @@ struct EngineT : mpcq_engine {
   }
   int sim_run(int K, int n_sub, double sim_dt) override {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_run needs mpcq_set_trajectories first");
+    if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
     if (K <= 0) return 0;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
@@ -929,9 +1003,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.2 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.3 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.2 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.3 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1225,6 +1299,130 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
                      (const double*)e->d_rp_in, (const int*)e->d_rp_int, (const int*)(e->d_rp_int + e->B));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+// ---- flight recorder (mpcq_record.hpp; the launches: EngineT::rec_snapshot / rec_write)
+#define MPCQ_RECORD_ALL 511
+int mpcq_record_start(mpcq_engine* e, const int32_t* quads, int32_t count, int32_t fields, int32_t every, int32_t capacity) {
+  ENTER(e);
+  Recorder& r = e->rec;
+  if (r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_start: a recording is active (mpcq_record_stop first)");
+  if (quads && count <= 0) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: count must be > 0");
+  if (fields == 0 || (fields & ~MPCQ_RECORD_ALL)) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: fields empty or unknown bits");
+  if (every < 1 || capacity < 1) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: every and capacity must be >= 1");
+  if (!e->nb && (fields & (MPCQ_RECORD_RGP_MU | MPCQ_RECORD_RGP_C))) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: RGP fields on an engine with nb = 0");
+  const int n = quads ? count : e->B;
+  std::vector<int> sel(n);
+  std::vector<char> seen(e->B, 0);
+  for (int j = 0; j < n; ++j) {
+    sel[j] = quads ? quads[j] : j;
+    if (sel[j] < 0 || sel[j] >= e->B) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: quadrotor index out of range");
+    if (seen[sel[j]]++) return fail(MPCQ_ERR_INVALID, "mpcq_record_start: duplicate quadrotor index");
+  }
+  Recorder nr;
+  nr.fields = fields; nr.every = every; nr.capacity = capacity; nr.count = n;
+  nr.sorted = sel;
+  std::sort(nr.sorted.begin(), nr.sorted.end());
+  nr.pos.resize(n);
+  for (int j = 0; j < n; ++j) nr.pos[j] = (int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), sel[j]) - nr.sorted.begin());
+  // the groups of mpcq_sim_steps (EngineT::sim_steps: the same `per`)
+  const int G = e->n_groups, per = ((e->B + G - 1) / G + 7) / 8 * 8;
+  for (int g = 0; g < G; ++g) {
+    const int g0 = std::min(e->B, g * per), g1 = std::min(e->B, g0 + per);
+    nr.glo.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g0) - nr.sorted.begin()));
+    nr.ghi.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g1) - nr.sorted.begin()));
+  }
+  auto alloc = [&](void** p, size_t bytes, const char* what) {
+    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) {
+      (void)hipGetLastError();
+      *p = nullptr;
+      return fail(MPCQ_ERR_DEVICE, std::string("mpcq_record_start: cannot allocate ") + std::to_string(bytes) + " bytes for " + what);
+    }
+    return 0;
+  };
+  int rc = alloc((void**)&nr.d_sel, (size_t)n * sizeof(int), "the selection");
+  for (int f = 0; f < mpcq::record::NF && !rc; ++f) {
+    if (!(fields >> f & 1)) continue;
+    const size_t elems = (size_t)capacity * n * mpcq::record::width(f, e->nb);
+    rc = f == mpcq::record::F_SOLVER ? alloc((void**)&nr.d_solver, elems * sizeof(int), "the solver field")
+                                     : alloc((void**)&nr.d_f[f], elems * sizeof(double), "a recorded field");
+  }
+  if (!rc && (fields & MPCQ_RECORD_DRAG)) rc = alloc((void**)&nr.d_snap, (size_t)n * mpcq::record::SNAP * sizeof(double), "the drag snapshot");
+  if (!rc && hipMemcpyAsync(nr.d_sel, nr.sorted.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    rc = fail(MPCQ_ERR_DEVICE, "mpcq_record_start: copy of the selection failed");
+  if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MPCQ_ERR_DEVICE, "mpcq_record_start: hipStreamSynchronize failed");
+  if (rc) { nr.release(); return rc; }
+  nr.period_of.reserve(capacity < (1 << 20) ? capacity : (1 << 20));
+  nr.on = true;
+  r = std::move(nr);
+  return 0;
+}
+int mpcq_record_info(mpcq_engine* e, int32_t* rows, int64_t* dropped, int64_t* periods) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_info: no active recording");
+  if (rows) *rows = r.rows;
+  if (dropped) *dropped = r.dropped;
+  if (periods) *periods = r.periods;
+  return 0;
+}
+extern "C++" {
+namespace {
+// rows [rows][count][W] on the device -> out [count][rows][W] in the caller's order
+template <typename V> int rec_read(mpcq_engine* e, const V* src, int W, V* out) {
+  const Recorder& r = e->rec;
+  const size_t n = (size_t)r.rows * r.count * W;
+  if (!n) return 0;
+  std::vector<V> tmp(n);
+  HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(V), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int j = 0; j < r.count; ++j)
+    for (int k = 0; k < r.rows; ++k)
+      std::memcpy(out + ((size_t)j * r.rows + k) * W, tmp.data() + ((size_t)k * r.count + r.pos[j]) * W, W * sizeof(V));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+int mpcq_record_get(mpcq_engine* e, int32_t field, double* out) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_get: no active recording");
+  if (field <= 0 || (field & (field - 1)) || !(field & r.fields) || field == MPCQ_RECORD_SOLVER)
+    return fail(MPCQ_ERR_INVALID, "mpcq_record_get: field is not one recorded double field (MPCQ_RECORD_SOLVER: mpcq_record_get_solver)");
+  if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
+  int f = 0;
+  while (!(field >> f & 1)) ++f;
+  return rec_read(e, (const double*)r.d_f[f], mpcq::record::width(f, e->nb), out);
+}
+int mpcq_record_get_solver(mpcq_engine* e, int32_t* out) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_get_solver: no active recording");
+  if (!(r.fields & MPCQ_RECORD_SOLVER)) return fail(MPCQ_ERR_INVALID, "mpcq_record_get_solver: MPCQ_RECORD_SOLVER was not recorded");
+  if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
+  return rec_read(e, (const int*)r.d_solver, 4, (int*)out);
+}
+int mpcq_record_get_periods(mpcq_engine* e, int64_t* out) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_get_periods: no active recording");
+  if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
+  for (int k = 0; k < r.rows; ++k) out[k] = r.period_of[k];
+  return 0;
+}
+int mpcq_record_clear(mpcq_engine* e) {
+  ENTER(e);
+  Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_clear: no active recording");
+  r.rows = 0; r.dropped = 0; r.period_of.clear();
+  return 0;
+}
+int mpcq_record_stop(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->rec.on) return fail(MPCQ_ERR_STATE, "mpcq_record_stop: no active recording");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the buffers)
+  e->rec.release();
   return 0;
 }
 

@@ -1,0 +1,112 @@
+// mpcq_record.hpp — the flight recorder (mpcq_record_start / _get): one row per selected quadrotor and recorded period, written by
+// launches placed around the period's step launch.  Included from mpcq_api.hip only; the step kernel and its state are untouched.
+//
+//  * record_snapshot_kernel, in front of the step launch (MPCQ_RECORD_DRAG only): x_pred_prev and has_prev the step starts from,
+//    which its post phase overwrites.
+//  * record_kernel, behind the step launch and in front of any plant launch: every requested field of the period, read from the
+//    device state the step left.  Each field is stored period-major, [capacity][count][width], so one launch writes one contiguous
+//    slab per field; lanes run over the flattened (quadrotor, element) index of the slab -- 64 consecutive lanes store 64
+//    consecutive values -- and read the per-quadrotor records contiguously (the reference row is the only gather).
+// Blocks of one wavefront, no LDS, no atomics; the write position (row) is host bookkeeping.
+#pragma once
+
+namespace mpcq {
+namespace record {
+
+// fields in bit order of include/mpcq.h MPCQ_RECORD_*: x_odom, x_ref, w, x_pred, cost, drag, rgp_mu, rgp_C, solver
+constexpr int NF = 9, F_XODOM = 0, F_XREF = 1, F_W = 2, F_XPRED = 3, F_COST = 4, F_DRAG = 5, F_MU = 6, F_C = 7, F_SOLVER = 8;
+constexpr int SNAP = NX + 1;   // snapshot row: x_pred_prev (13), has_prev
+__host__ __device__ inline int width(int f, int nb) {
+  switch (f) {
+    case F_XODOM: case F_XREF: case F_XPRED: return NX;
+    case F_W: return NU;
+    case F_COST: return 1;
+    case F_DRAG: return 6;
+    case F_MU: return 3 * nb;
+    case F_C: return 3 * nb * nb;
+    default: return 4;
+  }
+}
+
+template <typename TQ>
+struct Args {
+  const int* sel;      // selection, sorted [count]
+  int j0, n;           // the part of the selection this launch covers: [j0, j0 + n)
+  int count;           // selection size (row stride of a slab)
+  int row;             // write position
+  int blk[NF + 1];     // first block of each field; blk[NF] = blocks of the launch (a field not recorded has no blocks)
+  double* out[NF - 1]; // double fields [capacity][count][width]
+  int* solver;         // [capacity][count][4] int32
+  const double* snap;  // [count][SNAP]
+  const double* xmeas; const double* w; const double* xpred; const double* cost; const double* traj;
+  const int* tlen; const int* idx; const int* finished; const int* status; const int* qp_iter;
+  const TQ* mu; const TQ* C;
+  int Tmax, N, skip, nb;
+  double dt_pred;
+};
+
+__global__ void __launch_bounds__(64) record_snapshot_kernel(const int* sel, int j0, int n, const double* xpp, const int* has_prev, double* snap) {
+  const long t = (long)blockIdx.x * 64 + threadIdx.x;
+  if (t >= (long)n * SNAP) return;
+  const int jl = (int)(t / SNAP), k = (int)(t - (long)jl * SNAP), j = j0 + jl, b = sel[j];
+  snap[(size_t)j * SNAP + k] = k < NX ? xpp[(size_t)b * NX + k] : (double)has_prev[b];
+}
+
+template <typename TQ>
+__global__ void __launch_bounds__(64) record_kernel(const Args<TQ> a) {
+  const int bx = blockIdx.x;
+  int f = 0, first = 0;   // the field of this block (block-uniform; constant indices keep the argument arrays out of scratch)
+#pragma unroll
+  for (int k = 1; k < NF; ++k)
+    if (bx >= a.blk[k]) { f = k; first = a.blk[k]; }
+  const int W = width(f, a.nb);
+  const long t = (long)(bx - first) * 64 + threadIdx.x;
+  if (t >= (long)a.n * W) return;
+  const int jl = (int)(t / W), e = (int)(t - (long)jl * W), j = a.j0 + jl, b = a.sel[j];
+  const size_t o = ((size_t)a.row * a.count + j) * W + e;
+  switch (f) {
+    case F_XODOM: a.out[F_XODOM][o] = a.xmeas[(size_t)b * NX + e]; break;
+    case F_XREF: {   // row 0 of the chunk the step used: the post phase has advanced the cursor by one
+      const int idx = a.idx[b] - 1, len = a.tlen[b];
+      const long r = chunk_row(0, chunk_have(len, idx, a.N, a.skip), idx, a.skip, len);
+      a.out[F_XREF][o] = a.traj[((size_t)b * a.Tmax + r) * NX + e];
+      break;
+    }
+    case F_W: a.out[F_W][o] = a.w[(size_t)b * NU + e]; break;
+    case F_XPRED: a.out[F_XPRED][o] = a.xpred[(size_t)b * NX + e]; break;
+    case F_COST: a.out[F_COST][o] = a.cost[b]; break;
+    case F_DRAG: {   // compute_a_drag of the post phase (mpcq_kernels.hpp, step_kernel section 4) against the snapshot
+      double x[NX], xq[NX];
+      const double* sn = a.snap + (size_t)j * SNAP;
+      const bool hp = sn[NX] != 0.0;
+#pragma unroll
+      for (int k = 0; k < NX; ++k) { x[k] = a.xmeas[(size_t)b * NX + k]; xq[k] = hp ? sn[k] : x[k]; }
+      double R[9], Rq[9];
+      rotmat(x + 3, R);
+      rotmat(xq + 3, Rq);
+      const int c = e < 3 ? e : e - 3;
+      double vb = 0, vp = 0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (i == c) {
+          vb = R[i] * x[7] + R[3 + i] * x[8] + R[6 + i] * x[9];
+          vp = Rq[i] * xq[7] + Rq[3 + i] * xq[8] + Rq[6 + i] * xq[9];
+        }
+      a.out[F_DRAG][o] = e < 3 ? vb : (vb - vp) / a.dt_pred;
+      break;
+    }
+    case F_MU: a.out[F_MU][o] = (double)a.mu[(size_t)b * 3 * a.nb + e]; break;
+    case F_C: a.out[F_C][o] = (double)a.C[(size_t)b * 3 * a.nb * a.nb + e]; break;
+    default: {
+      int v;
+      if (e == 0) v = a.status[b];
+      else if (e == 1) v = a.qp_iter[b];
+      else if (e == 2) v = a.idx[b] - 1;
+      else v = a.finished[b];
+      a.solver[o] = v;
+    }
+  }
+}
+
+}  // namespace record
+}  // namespace mpcq

@@ -46,6 +46,12 @@ SOLVE_LOW_ACCURACY = 8
 REPLAN_DONE, REPLAN_SKIPPED, REPLAN_BAD_INPUT, REPLAN_SINGULAR, REPLAN_LIMITS, REPLAN_TOO_LONG = 0, 1, -1, -2, -3, -4
 
 
+# flight recorder fields (include/mpcq.h MPCQ_RECORD_*): name -> bit
+RECORD_FIELDS = {"x_odom": 1, "x_ref": 2, "w_odom": 4, "x_pred_odom": 8, "cost_solution": 16, "drag": 32, "rgp_mu": 64, "rgp_C": 128,
+                 "solver": 256}
+RECORD_DEFAULT = ("x_odom", "x_ref", "w_odom", "x_pred_odom", "cost_solution", "drag", "rgp_mu", "solver")
+
+
 class Engine:
     def __init__(self, cfg: EngineConfig, lib_path: str | None = None):
         self.cfg = cfg
@@ -146,6 +152,66 @@ class Engine:
         traj, lengths = np.zeros((self.B, tmax, NX)), np.zeros(self.B, np.int32)
         self._check(self.lib.mpcq_get_trajectories(self.h, _lib.d(traj), _lib.i(lengths)))
         return traj, lengths
+
+    # ---- flight recorder: per-period rows of selected quadrotors written on the device, read once
+    def record_start(self, quads=None, fields=RECORD_DEFAULT, every=1, capacity=1000):
+        """Record quadrotors `quads` (None: all, else indices in the order record_get returns them) from the next period on: the fields
+        named (RECORD_FIELDS; the default drops the RGP fields on an engine without RGP), every `every`-th period, up to `capacity`
+        rows per quadrotor (later periods are counted as dropped)."""
+        if fields is RECORD_DEFAULT and not self.nb:
+            fields = tuple(f for f in fields if not f.startswith("rgp"))
+        unknown = set(fields) - set(RECORD_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown record fields {sorted(unknown)}")
+        mask = 0
+        for f in fields:
+            mask |= RECORD_FIELDS[f]
+        q = None if quads is None else np.ascontiguousarray(quads, dtype=np.int32).reshape(-1)
+        self._check(self.lib.mpcq_record_start(self.h, _lib.i(q), 0 if q is None else len(q), mask, int(every), int(capacity)))
+        self._rec = dict(quads=np.arange(self.B, dtype=np.int32) if q is None else q.copy(), fields=mask)
+
+    def record_info(self):
+        """(rows, dropped, periods): rows recorded, periods dropped because the buffer was full, periods counted since record_start."""
+        rows, dropped, periods = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.lib.mpcq_record_info(self.h, ctypes.byref(rows), ctypes.byref(dropped), ctypes.byref(periods)))
+        return rows.value, dropped.value, periods.value
+
+    def record_get(self):
+        """The recording so far, keyed by the reference's log names: x_odom, x_ref, x_pred_odom [count,T,13], w_odom [count,T,4],
+        cost_solution [count,T], v_body, a_drag [count,T,3], rgp_mu_g_t [count,T,3,nb], rgp_C_g_t [count,T,3,nb,nb], status, qp_iter,
+        idx (the cursor the step used), finished [count,T] -- the fields recorded -- and period [T], quads [count], dropped."""
+        rows, dropped, _ = self.record_info()
+        rec = getattr(self, "_rec", None)
+        quads, mask = rec["quads"], rec["fields"]
+        n, nb = len(quads), self.nb
+        out = dict(period=np.zeros(rows, np.int64), quads=quads.copy(), dropped=dropped)
+        self._check(self.lib.mpcq_record_get_periods(self.h, _lib.l(out["period"])))
+
+        def get(bit, width):
+            a = np.zeros((n, rows, width))
+            self._check(self.lib.mpcq_record_get(self.h, bit, _lib.d(a)))
+            return a
+        for name, bit, shape in (("x_odom", 1, (NX,)), ("x_ref", 2, (NX,)), ("w_odom", 4, (NU,)), ("x_pred_odom", 8, (NX,)),
+                                 ("cost_solution", 16, ()), ("rgp_mu_g_t", 64, (3, nb)), ("rgp_C_g_t", 128, (3, nb, nb))):
+            if mask & bit:
+                out[name] = get(bit, int(np.prod(shape, dtype=np.int64))).reshape((n, rows) + shape)
+        if mask & 32:
+            d = get(32, 6)
+            out["v_body"], out["a_drag"] = d[:, :, 0:3].copy(), d[:, :, 3:6].copy()
+        if mask & 256:
+            sv = np.zeros((n, rows, 4), np.int32)
+            self._check(self.lib.mpcq_record_get_solver(self.h, _lib.i(sv)))
+            for k, name in enumerate(("status", "qp_iter", "idx", "finished")):
+                out[name] = sv[:, :, k].copy()
+        return out
+
+    def record_clear(self):
+        """Empty the buffers (rows and dropped to 0); selection, fields and the period count stay."""
+        self._check(self.lib.mpcq_record_clear(self.h))
+
+    def record_stop(self):
+        self._check(self.lib.mpcq_record_stop(self.h))
+        self._rec = None
 
     def set_reference(self, yref, yrefN):
         yref = self._f(yref, (self.B, self.N, NY))

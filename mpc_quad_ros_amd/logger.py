@@ -43,6 +43,35 @@ class SwarmLogger:
                 r[k].append(None)
         self._x_pred_prev = np.array(x_pred)
 
+    @classmethod
+    def from_recording(cls, engine, rec, control_dt, t0=0.0, t_cpu=None):
+        """A logger holding a flight recording (Engine.record_get()) in the rows log_step would have appended: quad_log(j) / save(path, j)
+        give the reference's layout for the j-th recorded quadrotor.  t_odom = t0 + period * control_dt; t_cpu: the given seconds, by
+        default the mean step-launch time of the engine's last mpcq_sim_steps call (mpcq_get_kernel_time)."""
+        lg = cls(engine)
+        count, T = len(rec["quads"]), len(rec["period"])
+        if t_cpu is None:
+            s, n = engine.get_kernel_time()
+            t_cpu = s / n if n else 0.0
+        r = lg.rows
+        for k in range(T):
+            r["x_odom"].append(rec["x_odom"][:, k]); r["x_pred_odom"].append(rec["x_pred_odom"][:, k]); r["x_ref"].append(rec["x_ref"][:, k])
+            r["t_odom"].append(np.full(count, t0 + rec["period"][k] * control_dt)); r["w_odom"].append(rec["w_odom"][:, k])
+            r["t_cpu"].append(np.full((count, 1), float(t_cpu))); r["cost_solution"].append(rec["cost_solution"][:, k])
+            if engine.nb and "rgp_mu_g_t" in rec:
+                nb = engine.nb
+                r["rgp_basis_vectors"].append(np.broadcast_to(engine.cfg.basis, (count, 3, nb)).copy())
+                r["rgp_mu_g_t"].append(rec["rgp_mu_g_t"][:, k])
+                r["rgp_C_g_t"].append(rec["rgp_C_g_t"][:, k] if "rgp_C_g_t" in rec else None)
+                r["rgp_theta"].append(np.broadcast_to(engine.cfg.theta, (count, 3, 3)).copy())
+                r["v_body"].append(rec["v_body"][:, k, :, None]); r["a_drag"].append(rec["a_drag"][:, k, :, None])
+            else:
+                for key in ("rgp_basis_vectors", "rgp_mu_g_t", "rgp_C_g_t", "rgp_theta", "v_body", "a_drag"):
+                    r[key].append(None)
+        if T:
+            lg._x_pred_prev = np.array(rec["x_pred_odom"][:, -1])
+        return lg
+
     def quad_log(self, b):
         """Dict for quadrotor b in the reference's pickle layout (arrays stacked over steps)."""
         out = {}
