@@ -395,6 +395,28 @@ int mpcq_record_clear(mpcq_engine* e);
 /* frees the buffers; recording off.  get / info / clear / stop without an active recording: MPCQ_ERR_STATE. */
 int mpcq_record_stop(mpcq_engine* e);
 
+/* ---- RGP read-out with uncertainty (since 0.6.4): GPEnsemble.predict(X_t, std=True) (src/gp/GPE.py:165-201) over RGP.predict
+ * (src/gp/RGP.py:168-229) for every quadrotor and axis, evaluated on the device.  With the axis' basis X, theta = (L, sigma_f, sigma_n),
+ * K_x^-1 as built at mpcq_create and the quadrotor's mu, C:
+ *     k*_j = sigma_f^2 exp(-(x - X_j)^2 / (2 L^2))     J = k* K_x^-1     mean = J mu     var = sigma_f^2 - J k*^T + J C J^T
+ * An engine created with MPCQ_FLAG_STATIC_GP answers with the static GP's posterior (src/gp/GP.py:135-179): the same mean and
+ * var = sigma_f^2 - J k*^T; C is not read.  All of it in float64: MPCQ_PRECISION_F32 engines convert mu and C as mpcq_get_rgp does, so
+ * the result is the formula applied to what mpcq_get_rgp returns.  var is returned as computed (rounding may leave a tiny negative
+ * number); the standard deviation is the caller's square root.
+ * xq [3,M] (per_quad = 0: one grid per axis, shared by the batch) or [B,3,M] (per_quad = 1: every quadrotor its own points).  Ordered
+ * behind everything the engine has enqueued, on all of its streams: it sees the state after the last period.  Blocks until the
+ * outputs are on the host; changes no engine state.  MPCQ_ERR_INVALID: xq NULL, both outputs NULL, M outside 1..4096, per_quad not
+ * 0 / 1.  MPCQ_ERR_STATE: nb = 0.  Non-finite query points are no error (a NaN point gives NaN outputs). */
+int mpcq_rgp_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t per_quad,
+                     double* mean /*[B,3,M] or NULL*/, double* var /*[B,3,M] or NULL*/);
+/* The same evaluation (bit for bit: one routine serves both) for rows row0 .. row0 + nrows - 1 of the active recording and the quadrotors
+ * of mpcq_record_start in the caller's order, read from the recorder's device buffers in place: nothing but the outputs travels to the
+ * host.  The row window bounds the size of the host arrays.  MPCQ_ERR_STATE: no active recording, nb = 0.  MPCQ_ERR_INVALID:
+ * MPCQ_RECORD_RGP_MU not recorded; var asked for without MPCQ_RECORD_RGP_C (MPCQ_FLAG_STATIC_GP engines need only the mean field);
+ * a window outside the rows recorded so far (nrows < 1 included); the argument rules of mpcq_rgp_predict. */
+int mpcq_record_predict(mpcq_engine* e, const double* xq /*[3,M]*/, int32_t M, int32_t row0, int32_t nrows,
+                        double* mean /*[count,nrows,3,M] or NULL*/, double* var /*[count,nrows,3,M] or NULL*/);
+
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)
  * regressors on the device, fp64.  The loop body never calls learn in the reference (offline estimator), so this is an

@@ -105,6 +105,8 @@ SYMBOLS = [
     ("mpcq_record_get_periods", ctypes.c_int, [_vp, _lp]),
     ("mpcq_record_clear", ctypes.c_int, [_vp]),
     ("mpcq_record_stop", ctypes.c_int, [_vp]),
+    ("mpcq_rgp_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
+    ("mpcq_record_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),
     ("mpcq_learn_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mpcq_learn_destroy", ctypes.c_int, [_vp]),

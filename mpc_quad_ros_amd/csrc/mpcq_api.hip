@@ -22,6 +22,7 @@
 #include "mpcq_replan.hpp"
 #include "mpcq_replan_nl.hpp"
 #include "mpcq_record.hpp"
+#include "mpcq_predict.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -212,6 +213,15 @@ struct mpcq_engine {
   double *d_rp_in = nullptr; size_t rp_in_elems = 0;   // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
   int* d_rp_int = nullptr;                             // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
+  // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
+  // allocated on first use and grown when needed (freed by EngineT)
+  std::vector<double> kxinv64;
+  struct PredictScratch {
+    double *Kinv = nullptr, *basis = nullptr, *xq = nullptr, *Jt = nullptr, *out = nullptr;
+    int* pos = nullptr;
+    size_t xq_elems = 0, jt_elems = 0, out_elems = 0, pos_elems = 0;
+  } pr;
+  virtual int rgp_predict(const double* xq, int M, int per_quad, double* mean, double* var) = 0;
   virtual TrajSlots traj_slots() = 0;
   virtual int init() = 0;
   virtual int reset() = 0;
@@ -247,6 +257,73 @@ struct mpcq_engine {
 
 namespace {
 
+// ---- RGP read-out: the one evaluation routine behind mpcq_rgp_predict (live state, TQ = the engine's precision) and
+// mpcq_record_predict (rows of the recorder's float64 buffers in place).  Set s reads mu / C at slab s (pos_host == nullptr) or at slab
+// (row0 + k) * count + pos[j] with (j, k) = (s / nrows, s % nrows); outputs [nsets][3][M] go straight to the caller's arrays.
+template <typename P> int pr_grow(P*& p, size_t& have, size_t need) {
+  if (have >= need) return 0;
+  if (p) { (void)hipFree(p); p = nullptr; have = 0; }
+  HIP_TRY(hipMalloc((void**)&p, need * sizeof(P)));
+  have = need;
+  return 0;
+}
+template <typename TQ>
+int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long C_stride, size_t nsets, const int* pos_host, int row0, int nrows, int count,
+                const double* xq, int M, int per_quad, double* mean, double* var) {
+  namespace pd = mpcq::predict;
+  mpcq_engine::PredictScratch& pr = e->pr;
+  const int nb = e->nb;
+  hipStream_t s = e->stream;
+  if (nsets * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "RGP read-out: too many (quadrotor, row) sets for one call");
+  if (!pr.Kinv) {
+    HIP_TRY(hipMalloc((void**)&pr.Kinv, (size_t)3 * nb * nb * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&pr.basis, (size_t)3 * nb * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(pr.Kinv, e->kxinv64.data(), (size_t)3 * nb * nb * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pr.basis, e->basis.data(), (size_t)3 * nb * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  const size_t nq = (per_quad ? nsets : 1) * 3 * (size_t)M, no = nsets * 3 * (size_t)M;
+  int rc;
+  if ((rc = pr_grow(pr.xq, pr.xq_elems, nq))) return rc;
+  if ((rc = pr_grow(pr.out, pr.out_elems, no * ((mean ? 1 : 0) + (var ? 1 : 0))))) return rc;
+  if (!per_quad && (rc = pr_grow(pr.Jt, pr.jt_elems, (size_t)3 * (nb + 1) * M))) return rc;
+  HIP_TRY(hipMemcpyAsync(pr.xq, xq, nq * sizeof(double), hipMemcpyHostToDevice, s));
+  if (pos_host) {
+    if ((rc = pr_grow(pr.pos, pr.pos_elems, (size_t)count))) return rc;
+    HIP_TRY(hipMemcpyAsync(pr.pos, pos_host, (size_t)count * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  pd::Args<TQ> a;
+  std::memset(&a, 0, sizeof(a));
+  a.mu = mu; a.C = var ? C : nullptr; a.mu_stride = mu_stride; a.C_stride = C_stride;
+  a.pos = pos_host ? pr.pos : nullptr; a.row0 = row0; a.nrows = nrows; a.count = count;
+  a.Kinv = pr.Kinv; a.basis = pr.basis;
+  for (int d = 0; d < 3; ++d) {
+    const double Lh = e->theta[3 * d], sf = e->theta[3 * d + 1];
+    a.sf2[d] = sf * sf; a.hl2[d] = 0.5 / (Lh * Lh);
+  }
+  a.mean = mean ? pr.out : nullptr;
+  a.var = var ? pr.out + (mean ? no : 0) : nullptr;
+  a.nb = nb; a.M = M;
+  if (per_quad) a.xq = pr.xq;
+  else {   // J^T and b of the shared grid, once per call
+    a.Jt = pr.Jt; a.bq = pr.Jt + (size_t)3 * nb * M;
+    const size_t lds = (size_t)pd::layout(nb, false, true).total * sizeof(double);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pd::predict_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(pd::predict_prep_kernel, dim3(3 * ((M + 63) / 64)), dim3(64), lds, s, (const double*)pr.xq, (const double*)pr.Kinv, (const double*)pr.basis,
+                       a.sf2[0], a.sf2[1], a.sf2[2], a.hl2[0], a.hl2[1], a.hl2[2], nb, M, pr.Jt, pr.Jt + (size_t)3 * nb * M);
+    HIP_TRY(hipGetLastError());
+  }
+  const bool stage = nb <= pd::STAGE_NB;
+  const size_t lds = (size_t)pd::layout(nb, stage && a.C, per_quad != 0).total * sizeof(double);
+  void (*k)(const pd::Args<TQ>) = stage ? &pd::predict_kernel<TQ, true> : &pd::predict_kernel<TQ, false>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, dim3((unsigned)(nsets * 3)), dim3(64), lds, s, a);
+  HIP_TRY(hipGetLastError());
+  if (mean) HIP_TRY(hipMemcpyAsync(mean, a.mean, no * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (var) HIP_TRY(hipMemcpyAsync(var, a.var, no * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
 template <typename T>
 struct EngineT : mpcq_engine {
   mpcq::DevModel<T> m;
@@ -277,7 +354,7 @@ struct EngineT : mpcq_engine {
     DeviceGuard guard(cfg.device);
     void* ptrs[] = {st.qp_work, st.chk, st.finished, d_cmd, st.stage, st.X, st.U, st.mu, st.C, st.xpp, st.yref, st.yrefN, st.w, st.xpred, st.cost, st.stats, st.has_prev, st.idx,
                     st.status, st.qp_iter, d_basis, d_Kxinv, d_Kx, d_xin, d_uin, d_tmp, d_traj, d_xs, d_vb, d_ad, d_tlen, d_stats5, d_order,
-                    d_rp_in, d_rp_int};
+                    d_rp_in, d_rp_int, pr.Kinv, pr.basis, pr.xq, pr.Jt, pr.out, pr.pos};
     for (void* p : ptrs)
       if (p) (void)hipFree(p);
     if (h_pin) (void)hipHostFree(h_pin);
@@ -420,6 +497,7 @@ struct EngineT : mpcq_engine {
       if ((rc = h2q(d_Kx, Kx.data(), (size_t)3 * nb * nb))) return rc;
     }
     m.basis = d_basis; m.Kxinv = d_Kxinv;
+    kxinv64 = Kxinv;   // (the device copy above is T-typed; mpcq_rgp_predict evaluates in double)
     const size_t Bz = B;
     if ((rc = dalloc(st.X, Bz * (N + 1) * 13))) return rc;
     if ((rc = dalloc(st.U, Bz * N * 4))) return rc;
@@ -738,6 +816,11 @@ struct EngineT : mpcq_engine {
     if (C && nb && (rc = q2h(C, st.C, (size_t)B * 3 * nb * nb))) return rc;
     return 0;
   }
+  // the live model: the static GP's posterior has no J C J^T term and does not read C (src/gp/GP.py:135-179)
+  int rgp_predict(const double* xq, int M, int per_quad, double* mean, double* var) override {
+    const bool fixed = (cfg.flags & MPCQ_FLAG_STATIC_GP) != 0;
+    return predict_run<T>(this, st.mu, 3L * nb, fixed ? nullptr : st.C, 3L * nb * nb, (size_t)B, nullptr, 0, 1, B, xq, M, per_quad, mean, var);
+  }
   int step(const double* x_meas, double* w_out, double* x_pred_out) override {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_step needs mpcq_set_trajectories first");
     // host buffers go through one pinned staging block so that the three copies are truly asynchronous and the
@@ -1003,9 +1086,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.3 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.4 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.3 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.4 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1424,6 +1507,37 @@ int mpcq_record_stop(mpcq_engine* e) {
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the buffers)
   e->rec.release();
   return 0;
+}
+
+// ---- RGP read-out (mpcq_predict.hpp; predict_run).  The engine's stream is behind every group stream of mpcq_sim_steps when that call
+// returns, and both calls run on it: they see the state after the last period.
+namespace {
+int predict_args(const char* who, const mpcq_engine* e, const double* xq, int32_t M, const double* mean, const double* var) {
+  if (!xq) return fail(MPCQ_ERR_INVALID, std::string(who) + ": null query points");
+  if (!mean && !var) return fail(MPCQ_ERR_INVALID, std::string(who) + ": mean and var are both NULL");
+  if (M < 1 || M > mpcq::predict::MAX_M) return fail(MPCQ_ERR_INVALID, std::string(who) + ": M outside 1..4096");
+  if (!e->nb) return fail(MPCQ_ERR_STATE, std::string(who) + ": engine has no RGP (nb = 0)");
+  return 0;
+}
+}  // namespace
+int mpcq_rgp_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t per_quad, double* mean, double* var) {
+  ENTER(e);
+  if (per_quad != 0 && per_quad != 1) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_predict: per_quad must be 0 or 1");
+  if (const int rc = predict_args("mpcq_rgp_predict", e, xq, M, mean, var)) return rc;
+  return e->rgp_predict(xq, M, per_quad, mean, var);
+}
+int mpcq_record_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t row0, int32_t nrows, double* mean, double* var) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_predict: no active recording");
+  if (const int rc = predict_args("mpcq_record_predict", e, xq, M, mean, var)) return rc;
+  const bool fixed = (e->cfg.flags & MPCQ_FLAG_STATIC_GP) != 0;
+  if (!(r.fields & MPCQ_RECORD_RGP_MU)) return fail(MPCQ_ERR_INVALID, "mpcq_record_predict: MPCQ_RECORD_RGP_MU was not recorded");
+  if (var && !fixed && !(r.fields & MPCQ_RECORD_RGP_C)) return fail(MPCQ_ERR_INVALID, "mpcq_record_predict: var needs MPCQ_RECORD_RGP_C in the recording");
+  if (row0 < 0 || nrows < 1 || (long long)row0 + nrows > r.rows) return fail(MPCQ_ERR_INVALID, "mpcq_record_predict: row window outside the rows recorded so far");
+  const int nb = e->nb;
+  return predict_run<double>(e, r.d_f[mpcq::record::F_MU], 3L * nb, fixed ? nullptr : r.d_f[mpcq::record::F_C], 3L * nb * nb, (size_t)r.count * nrows, r.pos.data(),
+                             row0, nrows, r.count, xq, M, 0, mean, var);
 }
 
 int mpcq_get_trajectories(mpcq_engine* e, double* traj, int32_t* len) {

@@ -319,6 +319,33 @@ class Engine:
         self._check(self.lib.mpcq_get_rgp(self.h, _lib.d(mu), _lib.d(C)))
         return mu, C
 
+    def rgp_predict(self, xq, var=True, per_quad=False):
+        """Posterior of every quadrotor's drag model at query points xq [3,M] (one grid per axis, shared by the batch) or, with
+        per_quad, [B,3,M]: mean [B,3,M], and with var the variance [B,3,M] (as computed: take np.sqrt for the reference's std)."""
+        xq = self._f(xq)
+        if xq.shape[:-1] != ((self.B, 3) if per_quad else (3,)):
+            raise ValueError(f"xq must be [B={self.B}, 3, M]" if per_quad else "xq must be [3, M]")
+        M = xq.shape[-1]
+        mean = np.zeros((self.B, 3, M))
+        v = np.zeros((self.B, 3, M)) if var else None
+        self._check(self.lib.mpcq_rgp_predict(self.h, _lib.d(xq), M, int(bool(per_quad)), _lib.d(mean), _lib.d(v)))
+        return (mean, v) if var else mean
+
+    def record_predict(self, xq, rows=None, var=True):
+        """rgp_predict for the recorded rows `rows` = (row0, nrows) (None: all recorded so far) of the active recording, evaluated from
+        the device buffers in place: mean [count,R,3,M] (and variance) for the recorded quadrotors in the order of record_start."""
+        xq = self._f(xq)
+        if xq.ndim != 2 or xq.shape[0] != 3:
+            raise ValueError("xq must be [3, M]")
+        recorded = self.record_info()[0]
+        row0, nrows = (0, recorded) if rows is None else (int(rows[0]), int(rows[1]))
+        n, M = len(self._rec["quads"]), xq.shape[1]
+        mean = np.zeros((n, nrows, 3, M))
+        v = np.zeros((n, nrows, 3, M)) if var else None
+        if rows is not None or nrows > 0:      # (nothing recorded yet: empty arrays)
+            self._check(self.lib.mpcq_record_predict(self.h, _lib.d(xq), M, row0, nrows, _lib.d(mean), _lib.d(v)))
+        return (mean, v) if var else mean
+
     # ---- fused path
     def step(self, x_meas):
         x = self._f(x_meas, (self.B, NX))

@@ -15,22 +15,49 @@ from .params import NU, NX, EngineConfig, QuadParams, hummingbird
 class _RGPView:
     """What callers read from ``quad_opt.gpe.gp[d]`` (src/mpc_controller_node.py:304-318)."""
 
-    def __init__(self, X, theta):
+    def __init__(self, X, theta, owner=None, axis=0):
         self.X = X
         self._theta = list(theta)
+        self._owner, self._axis = owner, axis
 
     def get_theta(self):
         return list(self._theta)
+
+    def predict(self, X_t_star, var=False, std=False):
+        """RGP.predict's numpy path (src/gp/RGP.py:168-229, without cov / return_Jt) for this axis of every quadrotor:
+        mean [B,M] (and the variance, or with std its square root)."""
+        x = np.asarray(X_t_star, dtype=np.float64)
+        assert x.ndim == 1, "X_t_star has to be a 1-D array"
+        xq = np.zeros((3, x.shape[0]))
+        xq[self._axis] = x
+        out = self._owner._engine().rgp_predict(xq, var=var or std)
+        if not (var or std):
+            return out[:, self._axis]
+        mean, v = out[0][:, self._axis], out[1][:, self._axis]
+        return mean, (np.sqrt(v) if std else v)
 
 
 class _GPEView:
     type = "RGP"
 
-    def __init__(self, basis, theta):
-        self.gp = [_RGPView(basis[d], theta[d]) for d in range(3)]
+    def __init__(self, basis, theta, engine=None):
+        self._engine = engine            # callable: the engine exists only after the view (quad_optimizer.__init__)
+        self.gp = [_RGPView(basis[d], theta[d], self, d) for d in range(3)]
 
     def get_theta(self):
         return [g.get_theta() for g in self.gp]
+
+    def predict(self, X_t, std=False):
+        """GPEnsemble.predict (src/gp/GPE.py:165-201) for the whole batch, evaluated on the device: X_t a list of three (M,)
+        arrays -> list of three [B,M] means (and, with std, the list of standard deviations np.sqrt(var))."""
+        assert len(X_t) == 3, "X_t has to be a list of length 3"
+        xs = [np.asarray(x, dtype=np.float64) for x in X_t]
+        for x in xs:
+            assert x.ndim == 1 and x.shape == xs[0].shape, "X_t has to hold three 1-D arrays of one length"
+        out = self._engine().rgp_predict(np.stack(xs), var=std)
+        if not std:
+            return [out[:, d] for d in range(3)]
+        return [out[0][:, d] for d in range(3)], [np.sqrt(out[1][:, d]) for d in range(3)]
 
 
 class quad_optimizer:
@@ -50,7 +77,7 @@ class quad_optimizer:
             theta = gpe.get("theta")
         self.cfg = EngineConfig(batch=batch, N=n_nodes, T=float(t_horizon), quad=self.quad, nb=nb, basis=basis,
                                 theta=theta, dt_pred=dt_pred, device=device, precision=precision)
-        self.gpe = _GPEView(self.cfg.basis, self.cfg.theta) if nb else None
+        self.gpe = _GPEView(self.cfg.basis, self.cfg.theta, lambda: self.engine) if nb else None
         self.np = 3 * nb
         self.batch = batch
         self.engine = Engine(self.cfg, lib_path=lib_path)
