@@ -1,6 +1,8 @@
 // mpcq_api.hip — C ABI (include/mpcq.h) over the HIP kernels in mpcq_kernels.hpp.
 // Host side of the engine: device allocations, precision dispatch, launches on a private
 // stream, HIP-event timing, optional RCCL reduction of the swarm statistics.
+// Device memory has two kinds of owner and no other: the arrays of fixed size register with the engine as they are allocated
+// (EngineT::dalloc -> mpcq_engine::arrays), scratch that is sized by a request is a DevBuf.  Kernel argument structs hold raw pointers and own nothing.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -170,6 +172,31 @@ bool spd_inverse(const std::vector<double>& A, int n, std::vector<double>& Ai) {
 struct TrajSlots {
   double* traj; int* len; int* idx; int* finished; const double* plant; int Tmax;
 };
+// Device scratch allocated on first use and replaced by a larger block when a request exceeds it (the contents are not kept).
+// Move-only: declaring the move assignment deletes the copy operations.
+template <typename P> struct DevBuf {
+  P* p = nullptr;
+  size_t elems = 0;
+  DevBuf& operator=(DevBuf&& o) {
+    release();
+    p = o.p; elems = o.elems;
+    o.p = nullptr; o.elems = 0;
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr; elems = 0;
+  }
+  hipError_t grow(size_t need) {
+    if (elems >= need) return hipSuccess;
+    release();
+    const hipError_t err = hipMalloc((void**)&p, need * sizeof(P));
+    if (err == hipSuccess) elems = need;
+    else p = nullptr;
+    return err;
+  }
+};
 // The flight recorder (mpcq_record_*): host bookkeeping and device buffers of a recording; the launches are EngineT's (rec_snapshot,
 // rec_write).  The selection is kept sorted (a group of mpcq_sim_steps covers a contiguous part of it); pos maps the caller's order to it.
 struct Recorder {
@@ -177,49 +204,67 @@ struct Recorder {
   int fields = 0, every = 1, capacity = 0, count = 0, rows = 0;
   long long dropped = 0, periods = 0;
   std::vector<int> sorted, pos;          // selection ascending; pos[j] = place of the caller's j-th quadrotor in `sorted`
-  std::vector<int> glo, ghi;             // part of `sorted` inside group g of mpcq_sim_steps: [glo[g], ghi[g])
+  std::vector<int> glo, ghi;             // part of `sorted` inside entry g of mpcq_engine::groups: [glo[g], ghi[g])
   std::vector<long long> period_of;      // period number of every row
-  int* d_sel = nullptr;                  // sorted selection
-  double* d_f[mpcq::record::NF - 1] = {};   // double fields, [capacity][count][width]
-  int* d_solver = nullptr;               // [capacity][count][4]
-  double* d_snap = nullptr;              // [count][SNAP]: x_pred_prev and has_prev in front of the step (MPCQ_RECORD_DRAG)
-  void release() {
-    void* ptrs[] = {d_sel, d_solver, d_snap};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (double* p : d_f) if (p) (void)hipFree(p);
-    *this = Recorder();
+  DevBuf<int> d_sel;                     // sorted selection
+  DevBuf<double> d_f[mpcq::record::NF - 1];   // double fields, [capacity][count][width]
+  DevBuf<int> d_solver;                  // [capacity][count][4]
+  DevBuf<double> d_snap;                 // [count][SNAP]: x_pred_prev and has_prev in front of the step (MPCQ_RECORD_DRAG)
+};
+// Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
+// on a stream of its own, the event that marks the end of its part of a call.
+struct Group {
+  int b0, n;
+  hipStream_t stream;
+  hipEvent_t done;
+};
+// Stream, events and communicator of an engine.  A base class of mpcq_engine because bases are destroyed behind members: every device
+// buffer the engine's members own is freed first, then the events, the streams and the communicator go, in this order.
+struct EngineQueues {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> kev;   // per-launch event pairs of the last sim_steps call
+  std::vector<Group> groups;     // [0, n_groups): the batch as mpcq_sim_steps runs it; [n_groups]: as one launch on `stream` (EngineT::init)
+  hipEvent_t gstart = nullptr;   // more than one group: the other groups' streams start behind it
+  void* comm = nullptr;
+  bool comm_borrowed = false;   // comm belongs to another engine of this process (mpcq_comm_share)
+  ~EngineQueues() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    for (hipEvent_t ev : kev) (void)hipEventDestroy(ev);
+    for (const Group& g : groups) if (g.done) (void)hipEventDestroy(g.done);
+    if (gstart) (void)hipEventDestroy(gstart);
+    for (const Group& g : groups) if (g.stream != stream) (void)hipStreamDestroy(g.stream);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (comm && !comm_borrowed && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
   }
 };
-struct mpcq_engine {
-  virtual ~mpcq_engine() {}
+struct mpcq_engine : EngineQueues {
+  // (deleted with the engine's device current, mpcq_destroy: the destructors of the members free device memory, and a guard in a
+  //  destructor's body would be gone before the first of them runs)
+  virtual ~mpcq_engine() { for (void* p : arrays) (void)hipFree(p); }
   mpcq_config cfg;
   std::vector<double> basis, theta;
   int B = 0, N = 0, nb = 0, threads = 64;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_time = 0;
   bool have_traj = false, timed = false;
   bool tuning_env = false;   // MPCQ_TUNING=1: measurement scripts may override tuning fields through the environment
-  void* comm = nullptr;
-  bool comm_borrowed = false;   // comm belongs to another engine of this process (mpcq_comm_share)
   int nranks = 1;
+  std::vector<void*> arrays;     // the device arrays of fixed size (EngineT::dalloc), freed with the engine
   double* d_stats5 = nullptr;
   int n_groups = 1;              // groups of mpcq_sim_steps (mpcq_tuning.groups; EngineT::init)
-  std::vector<hipEvent_t> kev;   // per-launch event pairs of the last sim_steps call
   double ktime = 0, kmin = 0, kmax = 0;   // HIP-event time of the timed step-kernel launches: total, fastest, slowest
   int klaunches = 0;
   bool have_sim = false;         // mpcq_sim_reset has set the plant state
-  // staging of mpcq_replan / mpcq_replace_trajectories (allocated on first use, grown when needed; freed by EngineT)
-  double *d_rp_in = nullptr; size_t rp_in_elems = 0;   // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
-  int* d_rp_int = nullptr;                             // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
+  // staging of mpcq_replan / mpcq_replace_trajectories
+  DevBuf<double> d_rp_in;        // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
+  DevBuf<int> d_rp_int;          // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
-  // allocated on first use and grown when needed (freed by EngineT)
   std::vector<double> kxinv64;
   struct PredictScratch {
-    double *Kinv = nullptr, *basis = nullptr, *xq = nullptr, *Jt = nullptr, *out = nullptr;
-    int* pos = nullptr;
-    size_t xq_elems = 0, jt_elems = 0, out_elems = 0, pos_elems = 0;
+    DevBuf<double> Kinv, basis, xq, Jt, out;
+    DevBuf<int> pos;
   } pr;
   virtual int rgp_predict(const double* xq, int M, int per_quad, double* mean, double* var) = 0;
   virtual TrajSlots traj_slots() = 0;
@@ -260,13 +305,6 @@ namespace {
 // ---- RGP read-out: the one evaluation routine behind mpcq_rgp_predict (live state, TQ = the engine's precision) and
 // mpcq_record_predict (rows of the recorder's float64 buffers in place).  Set s reads mu / C at slab s (pos_host == nullptr) or at slab
 // (row0 + k) * count + pos[j] with (j, k) = (s / nrows, s % nrows); outputs [nsets][3][M] go straight to the caller's arrays.
-template <typename P> int pr_grow(P*& p, size_t& have, size_t need) {
-  if (have >= need) return 0;
-  if (p) { (void)hipFree(p); p = nullptr; have = 0; }
-  HIP_TRY(hipMalloc((void**)&p, need * sizeof(P)));
-  have = need;
-  return 0;
-}
 template <typename TQ>
 int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long C_stride, size_t nsets, const int* pos_host, int row0, int nrows, int count,
                 const double* xq, int M, int per_quad, double* mean, double* var) {
@@ -275,41 +313,42 @@ int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long 
   const int nb = e->nb;
   hipStream_t s = e->stream;
   if (nsets * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "RGP read-out: too many (quadrotor, row) sets for one call");
-  if (!pr.Kinv) {
-    HIP_TRY(hipMalloc((void**)&pr.Kinv, (size_t)3 * nb * nb * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&pr.basis, (size_t)3 * nb * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(pr.Kinv, e->kxinv64.data(), (size_t)3 * nb * nb * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(pr.basis, e->basis.data(), (size_t)3 * nb * sizeof(double), hipMemcpyHostToDevice, s));
+  if (!pr.Kinv.p || !pr.basis.p) {
+    HIP_TRY(pr.Kinv.grow((size_t)3 * nb * nb));
+    HIP_TRY(pr.basis.grow((size_t)3 * nb));
+    HIP_TRY(hipMemcpyAsync(pr.Kinv.p, e->kxinv64.data(), (size_t)3 * nb * nb * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pr.basis.p, e->basis.data(), (size_t)3 * nb * sizeof(double), hipMemcpyHostToDevice, s));
   }
   const size_t nq = (per_quad ? nsets : 1) * 3 * (size_t)M, no = nsets * 3 * (size_t)M;
-  int rc;
-  if ((rc = pr_grow(pr.xq, pr.xq_elems, nq))) return rc;
-  if ((rc = pr_grow(pr.out, pr.out_elems, no * ((mean ? 1 : 0) + (var ? 1 : 0))))) return rc;
-  if (!per_quad && (rc = pr_grow(pr.Jt, pr.jt_elems, (size_t)3 * (nb + 1) * M))) return rc;
-  HIP_TRY(hipMemcpyAsync(pr.xq, xq, nq * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(pr.xq.grow(nq));
+  HIP_TRY(pr.out.grow(no * ((mean ? 1 : 0) + (var ? 1 : 0))));
+  if (!per_quad) HIP_TRY(pr.Jt.grow((size_t)3 * (nb + 1) * M));
+  HIP_TRY(hipMemcpyAsync(pr.xq.p, xq, nq * sizeof(double), hipMemcpyHostToDevice, s));
   if (pos_host) {
-    if ((rc = pr_grow(pr.pos, pr.pos_elems, (size_t)count))) return rc;
-    HIP_TRY(hipMemcpyAsync(pr.pos, pos_host, (size_t)count * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(pr.pos.grow((size_t)count));
+    HIP_TRY(hipMemcpyAsync(pr.pos.p, pos_host, (size_t)count * sizeof(int), hipMemcpyHostToDevice, s));
   }
   pd::Args<TQ> a;
   std::memset(&a, 0, sizeof(a));
   a.mu = mu; a.C = var ? C : nullptr; a.mu_stride = mu_stride; a.C_stride = C_stride;
-  a.pos = pos_host ? pr.pos : nullptr; a.row0 = row0; a.nrows = nrows; a.count = count;
-  a.Kinv = pr.Kinv; a.basis = pr.basis;
+  a.pos = pos_host ? pr.pos.p : nullptr; a.row0 = row0; a.nrows = nrows; a.count = count;
+  a.Kinv = pr.Kinv.p; a.basis = pr.basis.p;
   for (int d = 0; d < 3; ++d) {
     const double Lh = e->theta[3 * d], sf = e->theta[3 * d + 1];
     a.sf2[d] = sf * sf; a.hl2[d] = 0.5 / (Lh * Lh);
   }
-  a.mean = mean ? pr.out : nullptr;
-  a.var = var ? pr.out + (mean ? no : 0) : nullptr;
+  a.mean = mean ? pr.out.p : nullptr;
+  a.var = var ? pr.out.p + (mean ? no : 0) : nullptr;
   a.nb = nb; a.M = M;
-  if (per_quad) a.xq = pr.xq;
+  if (per_quad) a.xq = pr.xq.p;
   else {   // J^T and b of the shared grid, once per call
-    a.Jt = pr.Jt; a.bq = pr.Jt + (size_t)3 * nb * M;
+    const double* d_xq = pr.xq.p;
+    double *Jt = pr.Jt.p, *bq = Jt + (size_t)3 * nb * M;
+    a.Jt = Jt; a.bq = bq;
     const size_t lds = (size_t)pd::layout(nb, false, true).total * sizeof(double);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pd::predict_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(pd::predict_prep_kernel, dim3(3 * ((M + 63) / 64)), dim3(64), lds, s, (const double*)pr.xq, (const double*)pr.Kinv, (const double*)pr.basis,
-                       a.sf2[0], a.sf2[1], a.sf2[2], a.hl2[0], a.hl2[1], a.hl2[2], nb, M, pr.Jt, pr.Jt + (size_t)3 * nb * M);
+    hipLaunchKernelGGL(pd::predict_prep_kernel, dim3(3 * ((M + 63) / 64)), dim3(64), lds, s, d_xq, a.Kinv, a.basis,
+                       a.sf2[0], a.sf2[1], a.sf2[2], a.hl2[0], a.hl2[1], a.hl2[2], nb, M, Jt, bq);
     HIP_TRY(hipGetLastError());
   }
   const bool stage = nb <= pd::STAGE_NB;
@@ -336,42 +375,23 @@ struct EngineT : mpcq_engine {
   std::vector<double> hbufd;
   T *d_basis = nullptr, *d_Kxinv = nullptr, *d_Kx = nullptr;
   double* h_pin = nullptr;   // pinned staging of the host-buffer step: [x_meas B*13 | w B*4 | x_pred B*13]
-  double *d_xin = nullptr, *d_uin = nullptr, *d_tmp = nullptr, *d_traj = nullptr, *d_xs = nullptr, *d_vb = nullptr, *d_ad = nullptr;
+  double *d_xin = nullptr, *d_uin = nullptr, *d_tmp = nullptr, *d_xs = nullptr, *d_vb = nullptr, *d_ad = nullptr;
+  DevBuf<double> d_traj;     // [B][Tmax][13] (mpcq_set_trajectories)
   int* d_tlen = nullptr;
   int* d_order = nullptr;    // launch order of the lockstep periods (order_kernel); used when the batch exceeds what the device holds at once
   bool use_order = false;
   bool split_plant = false;   // the plant update between two lockstep periods as its own launch (streaming batches), see sim_steps
-  // mpcq_sim_steps with tune.groups > 1: the batch as n_groups contiguous groups, each advancing in lockstep on a stream of its own (sim_steps)
-  std::vector<hipStream_t> gstreams;
-  std::vector<hipEvent_t> gdone;
-  hipEvent_t gstart = nullptr;
-  double* d_cmd = nullptr;   // [B*8] rotor thrusts, collective thrust, body rates (mpcq_get_command); also the chunk read-back
-  size_t cmd_elems = 0;
+  DevBuf<double> d_cmd;      // [B*8] rotor thrusts, collective thrust, body rates (mpcq_get_command); also the chunk read-back
   std::vector<T> hbuf;
   std::vector<double> Kx;
 
-  ~EngineT() override {
-    DeviceGuard guard(cfg.device);
-    void* ptrs[] = {st.qp_work, st.chk, st.finished, d_cmd, st.stage, st.X, st.U, st.mu, st.C, st.xpp, st.yref, st.yrefN, st.w, st.xpred, st.cost, st.stats, st.has_prev, st.idx,
-                    st.status, st.qp_iter, d_basis, d_Kxinv, d_Kx, d_xin, d_uin, d_tmp, d_traj, d_xs, d_vb, d_ad, d_tlen, d_stats5, d_order,
-                    d_rp_in, d_rp_int, pr.Kinv, pr.basis, pr.xq, pr.Jt, pr.out, pr.pos};
-    for (void* p : ptrs)
-      if (p) (void)hipFree(p);
-    if (h_pin) (void)hipHostFree(h_pin);
-    rec.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    for (hipEvent_t ev : kev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : gdone) (void)hipEventDestroy(ev);
-    if (gstart) (void)hipEventDestroy(gstart);
-    for (hipStream_t gs : gstreams) if (gs != stream) (void)hipStreamDestroy(gs);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (comm && !comm_borrowed && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
-  }
+  ~EngineT() override { if (h_pin) (void)hipHostFree(h_pin); }
 
-  TrajSlots traj_slots() override { return TrajSlots{d_traj, d_tlen, st.idx, st.finished, d_xs, m.Tmax}; }
+  TrajSlots traj_slots() override { return TrajSlots{d_traj.p, d_tlen, st.idx, st.finished, d_xs, m.Tmax}; }
+  // a zero-filled device array of n elements (at least one: nb = 0) that lives as long as the engine
   template <typename P> int dalloc(P*& p, size_t n) {
     HIP_TRY(hipMalloc((void**)&p, (n ? n : 1) * sizeof(*p)));
+    arrays.push_back(p);
     HIP_TRY(hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(*p), stream));
     return 0;
   }
@@ -577,7 +597,6 @@ struct EngineT : mpcq_engine {
       return fail(MPCQ_ERR_INVALID, layout == 0 ? "per-instance working set exceeds 160 KiB LDS with the stage records in LDS (tune.stage_mem = 1)"
                                                 : "per-instance working set exceeds 160 KiB LDS (N/nb too large for this precision)");
     m.gab = layout;
-    const bool gab = layout != 0;
     if (env && getenv("MPCQ_VERBOSE"))
       fprintf(stderr, "mpcq: layout %d (%s), LDS %zu B per instance, %zu instances per CU; layouts 0/1/2: %zu/%zu/%zu B, %zu/%zu/%zu per CU\n", layout,
               layout == 0 ? "all LDS" : (layout == 1 ? "stage records in global memory" : "compact: stage records and gains in global memory"), bytes[layout], occ[layout],
@@ -614,13 +633,16 @@ struct EngineT : mpcq_engine {
       n_groups = ienv("MPCQ_GROUPS", tu.groups > 0 ? tu.groups : ((size_t)B > resident ? MPCQ_AUTO_GROUPS : 1));
       if (n_groups < 1) n_groups = 1;
       while (n_groups > 1 && B / n_groups < 8) n_groups -= 1;    // (a group holds at least one quadrotor of every launch-order class)
-      for (int g = 0; g < n_groups && n_groups > 1; ++g) {   // (group 0 runs on the engine's own stream: one hardware queue less)
-        hipStream_t gs = stream; hipEvent_t ev;
-        if (g > 0) HIP_TRY(hipStreamCreateWithFlags(&gs, hipStreamNonBlocking));
-        gstreams.push_back(gs);
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); gdone.push_back(ev);
+      const int per = ((B + n_groups - 1) / n_groups + 7) / 8 * 8;   // quadrotors per group (the last one takes what is left)
+      for (int g = 0; g < n_groups; ++g) {   // (group 0 runs on the engine's own stream: one hardware queue less)
+        const int b0 = std::min(B, g * per);
+        groups.push_back(Group{b0, std::min(B, b0 + per) - b0, stream, nullptr});
+        if (g == 0) continue;
+        HIP_TRY(hipStreamCreateWithFlags(&groups[g].stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&groups[g].done, hipEventDisableTiming));
       }
       if (n_groups > 1) HIP_TRY(hipEventCreateWithFlags(&gstart, hipEventDisableTiming));
+      groups.push_back(Group{0, B, stream, nullptr});   // mpcq_solve, mpcq_step, mpcq_step_device_async: always one launch over the batch
     }
     kstep = ks[layout];
     krun = kr[layout];
@@ -628,7 +650,6 @@ struct EngineT : mpcq_engine {
     if (!generic)
       if (auto k = spec_run(N, nb, layout, (T*)nullptr)) krun = k;
 #endif
-    (void)gab;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(krun), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kstep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mpcq::regress_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -647,12 +668,11 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemsetAsync(st.status, 0, Bz * sizeof(int), stream));
     HIP_TRY(hipMemsetAsync(st.qp_iter, 0, Bz * sizeof(int), stream));
     HIP_TRY(hipMemsetAsync(st.finished, 0, Bz * sizeof(int), stream));
+    std::vector<T> h((size_t)B * 3 * nb * nb);   // (read by the copy below: lives until the synchronise)
     if (nb) {  // C_0 = K_x for every instance and axis
-      std::vector<T> h((size_t)B * 3 * nb * nb);
       for (size_t b = 0; b < Bz; ++b)
         for (size_t i = 0; i < (size_t)3 * nb * nb; ++i) h[b * 3 * nb * nb + i] = (T)Kx[i];
       HIP_TRY(hipMemcpyAsync(st.C, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
@@ -662,16 +682,15 @@ struct EngineT : mpcq_engine {
     if (Tmax <= 0) return fail(MPCQ_ERR_INVALID, "Tmax must be positive");
     for (int b = 0; b < B; ++b)
       if (len[b] <= 0 || len[b] > Tmax) return fail(MPCQ_ERR_INVALID, "trajectory length out of range");
-    if (d_traj && m.Tmax != Tmax) { (void)hipFree(d_traj); d_traj = nullptr; }
-    if (!d_traj) HIP_TRY(hipMalloc((void**)&d_traj, (size_t)B * Tmax * 13 * sizeof(double)));
+    HIP_TRY(d_traj.grow((size_t)B * Tmax * 13));
     m.Tmax = Tmax;
     int rc;
-    if ((rc = h2d(d_traj, traj, (size_t)B * Tmax * 13))) return rc;
+    if ((rc = h2d(d_traj.p, traj, (size_t)B * Tmax * 13))) return rc;
     HIP_TRY(hipMemcpyAsync(d_tlen, len, (size_t)B * sizeof(int), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(st.idx, 0, (size_t)B * sizeof(int), stream));
     HIP_TRY(hipMemsetAsync(st.finished, 0, (size_t)B * sizeof(int), stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    st.traj = d_traj;
+    st.traj = d_traj.p;
     have_traj = true;
     return 0;
   }
@@ -716,8 +735,8 @@ struct EngineT : mpcq_engine {
   void rec_snapshot(hipStream_t s, int j0, int j1) {
     const int n = j1 - j0;
     if (!(rec.fields & MPCQ_RECORD_DRAG) || n <= 0) return;
-    hipLaunchKernelGGL(mpcq::record::record_snapshot_kernel, dim3((n * mpcq::record::SNAP + 63) / 64), dim3(64), 0, s, (const int*)rec.d_sel, j0, n,
-                       (const double*)st.xpp, (const int*)st.has_prev, rec.d_snap);
+    hipLaunchKernelGGL(mpcq::record::record_snapshot_kernel, dim3((n * mpcq::record::SNAP + 63) / 64), dim3(64), 0, s, (const int*)rec.d_sel.p, j0, n,
+                       (const double*)st.xpp, (const int*)st.has_prev, rec.d_snap.p);
   }
   // behind the step launch, in front of any plant launch: row `row` of every recorded field for the selection part [j0, j1)
   void rec_write(hipStream_t s, int j0, int j1, int row, const double* xmeas) {
@@ -725,15 +744,15 @@ struct EngineT : mpcq_engine {
     if (n <= 0) return;
     mpcq::record::Args<T> a;
     std::memset(&a, 0, sizeof(a));
-    a.sel = rec.d_sel; a.j0 = j0; a.n = n; a.count = rec.count; a.row = row;
+    a.sel = rec.d_sel.p; a.j0 = j0; a.n = n; a.count = rec.count; a.row = row;
     long blocks = 0;
     for (int f = 0; f < mpcq::record::NF; ++f) {
       a.blk[f] = (int)blocks;
       if (rec.fields >> f & 1) blocks += ((long)n * mpcq::record::width(f, nb) + 63) / 64;
     }
     a.blk[mpcq::record::NF] = (int)blocks;
-    for (int f = 0; f < mpcq::record::NF - 1; ++f) a.out[f] = rec.d_f[f];
-    a.solver = rec.d_solver; a.snap = rec.d_snap;
+    for (int f = 0; f < mpcq::record::NF - 1; ++f) a.out[f] = rec.d_f[f].p;
+    a.solver = rec.d_solver.p; a.snap = rec.d_snap.p;
     a.xmeas = xmeas; a.w = st.w; a.xpred = st.xpred; a.cost = st.cost; a.traj = st.traj;
     a.tlen = st.tlen; a.idx = st.idx; a.finished = st.finished; a.status = st.status; a.qp_iter = st.qp_iter;
     a.mu = st.mu; a.C = st.C;
@@ -742,9 +761,7 @@ struct EngineT : mpcq_engine {
   }
   // one lockstep period of the quadrotors [b0, b0 + nq) on stream `strm`; ev_begin (if any) is recorded in front of the STEP kernel, behind
   // the ordering launch, so that the event pairs of sim_steps time the step kernel alone
-  void launch_period(const mpcq::DevState<T>& s, int mode, hipEvent_t ev_begin = nullptr, hipStream_t strm = nullptr, int b0 = 0, int nq = -1) {
-    if (!strm) strm = stream;
-    if (nq < 0) nq = B;
+  void launch_period(const mpcq::DevState<T>& s, int mode, hipEvent_t ev_begin, hipStream_t strm, int b0, int nq) {
     mpcq::DevState<T> so = s;
     so.b0 = b0;
     if (use_order) {   // (reads qp_iter of the previous period; a permutation by construction whatever qp_iter holds: order_bin is total)
@@ -754,19 +771,29 @@ struct EngineT : mpcq_engine {
     if (ev_begin) (void)hipEventRecord(ev_begin, strm);
     hipLaunchKernelGGL(kstep, dim3(nq), dim3(64), lds_bytes, strm, m, so, mode);
   }
-  int launch_step(int mode) {
-    HIP_TRY(hipEventRecord(ev0, stream));
-    launch_period(st, mode);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, stream));
-    timed = true;
+  // One period of groups[gi], the only place that issues one.  On the group's stream, in this order: the recorder's snapshot (row >= 0:
+  // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the plant kernel
+  // (plant: s.run_nsub substeps of s.run_dt on s.run_x).  Every event is optional.  The caller asks hipGetLastError once it has issued
+  // all it has to issue.
+  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
+    const Group& g = groups[gi];
+    if (g.n <= 0) return 0;
+    if (row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
+    if (ev_front) HIP_TRY(hipEventRecord(ev_front, g.stream));
+    launch_period(s, mode, ev_step, g.stream, g.b0, g.n);
+    if (ev_end) HIP_TRY(hipEventRecord(ev_end, g.stream));
+    if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
+    if (plant)
+      hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g.n + 63) / 64), dim3(64), 0, g.stream, m, s.run_x + (size_t)g.b0 * 13, st.w + (size_t)g.b0 * 4, s.run_nsub, s.run_dt, g.n);
     return 0;
   }
   int solve(const double* x0) override {
     int rc;
     if ((rc = h2d(d_xin, x0, (size_t)B * 13))) return rc;
     st.x_meas = d_xin;
-    if ((rc = launch_step(0))) return rc;
+    if ((rc = period(n_groups, st, 0, -1, ev0, nullptr, ev1, false))) return rc;
+    HIP_TRY(hipGetLastError());
+    timed = true;
     HIP_TRY(hipStreamSynchronize(stream));
     return chk_after();
   }
@@ -831,10 +858,9 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemcpyAsync(d_xin, h_pin, nx * sizeof(double), hipMemcpyHostToDevice, stream));
     st.x_meas = d_xin;
     int rc;
-    const int row = rec.on ? rec_next_row() : -1;
-    if (row >= 0) rec_snapshot(stream, 0, rec.count);
-    if ((rc = launch_step(mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode()))) return rc;
-    if (row >= 0) rec_write(stream, 0, rec.count, row, d_xin);
+    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, ev0, nullptr, ev1, false))) return rc;
+    HIP_TRY(hipGetLastError());
+    timed = true;
     HIP_TRY(hipMemcpyAsync(h_pin + nx, st.w, nw * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (x_pred_out) HIP_TRY(hipMemcpyAsync(h_pin + nx + nw, st.xpred, nx * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -847,13 +873,9 @@ struct EngineT : mpcq_engine {
     mpcq::DevState<T> s2 = st;   // measurement and control are float64 in every precision (DevState::x_meas / w)
     s2.x_meas = d_x;
     s2.w_ext = d_w;   // the engine's own control record st.w is written as well (mpcq_get_command, mpcq_sim_plant_period(w = NULL))
-    const int row = rec.on ? rec_next_row() : -1;
-    if (row >= 0) rec_snapshot(stream, 0, rec.count);
-    HIP_TRY(hipEventRecord(ev0, stream));
-    launch_period(s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode());
+    int rc;
+    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, stream));
-    if (row >= 0) rec_write(stream, 0, rec.count, row, d_x);
     timed = true;
     return chk_after();   // (synchronises in the checked build only)
   }
@@ -875,44 +897,25 @@ struct EngineT : mpcq_engine {
     // (split_plant, see create): every update is a launch of the plant kernel.  Same arithmetic, same results either way.
     const bool split = split_plant;
     s2.run_x = d_xs; s2.run_steps = 1; s2.run_nsub = n_sub; s2.run_dt = sim_dt;
+    // Groups (see init): the K periods {order, step, plant} of a group go to its stream, issued period by period round the groups so that
+    // the host feeds every queue.  The group streams start behind everything issued on the engine's stream and the engine's stream
+    // continues behind all of them; a batch that is one group runs on the engine's stream and needs neither.  Event pairs: group 0's
+    // launches (with more groups, a launch of B / G quadrotors that shares the device).
     const int G = n_groups;
-    if (G > 1) {
-      // Groups (see init): group g = quadrotors [g0, g1), its K periods {order, step, plant} on gstreams[g], issued period by period round the
-      // groups so that the host feeds every queue.  The group streams start behind everything issued on the engine's stream and the
-      // engine's stream continues behind all of them.  Event pairs: group 0's launches (a launch of B / G quadrotors that shares the device).
-      HIP_TRY(hipEventRecord(gstart, stream));
-      for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(gstreams[g], gstart, 0));
-      const int per = ((B + G - 1) / G + 7) / 8 * 8;   // quadrotors per group (the last one takes what is left)
-      for (int k = 0; k < K; ++k) {
-        const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of group g cover the selection inside [g0, g1))
-        for (int g = 0; g < G; ++g) {
-          const int g0 = g * per, g1 = std::min(B, g0 + per);
-          if (g0 >= g1) continue;
-          const bool timed_launch = g == 0 && k % stride == 0;
-          const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
-          if (row >= 0) rec_snapshot(gstreams[g], rec.glo[g], rec.ghi[g]);
-          launch_period(s2, mode, timed_launch ? kev[2 * (k / stride)] : nullptr, gstreams[g], g0, g1 - g0);
-          if (timed_launch) HIP_TRY(hipEventRecord(kev[2 * (k / stride) + 1], gstreams[g]));
-          if (row >= 0) rec_write(gstreams[g], rec.glo[g], rec.ghi[g], row, d_xs);
-          if (split || k == K - 1)
-            hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g1 - g0 + 63) / 64), dim3(64), 0, gstreams[g], m, d_xs + (size_t)g0 * 13, st.w + (size_t)g0 * 4, n_sub, sim_dt, g1 - g0);
-        }
-      }
-      for (int g = 1; g < G; ++g) {
-        HIP_TRY(hipEventRecord(gdone[g], gstreams[g]));
-        HIP_TRY(hipStreamWaitEvent(stream, gdone[g], 0));
-      }
-    } else
+    if (G > 1) HIP_TRY(hipEventRecord(gstart, stream));
+    for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(groups[g].stream, gstart, 0));
+    int rc;
     for (int k = 0; k < K; ++k) {
-      const bool timed_launch = k % stride == 0;
+      const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of a group cover the selection inside it)
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
-      const int row = rec.on ? rec_next_row() : -1;
-      if (row >= 0) rec_snapshot(stream, 0, rec.count);
-      launch_period(s2, mode, timed_launch ? kev[2 * (k / stride)] : nullptr);
-      if (timed_launch) HIP_TRY(hipEventRecord(kev[2 * (k / stride) + 1], stream));
-      if (row >= 0) rec_write(stream, 0, rec.count, row, d_xs);
-      if (split || k == K - 1)
-        hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, stream, m, d_xs, st.w, n_sub, sim_dt, B);
+      for (int g = 0; g < G; ++g) {
+        hipEvent_t* pair = g == 0 && k % stride == 0 ? &kev[2 * (k / stride)] : nullptr;
+        if ((rc = period(g, s2, mode, row, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
+      }
+    }
+    for (int g = 1; g < G; ++g) {
+      HIP_TRY(hipEventRecord(groups[g].done, groups[g].stream));
+      HIP_TRY(hipStreamWaitEvent(stream, groups[g].done, 0));
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, stream));
@@ -966,21 +969,15 @@ struct EngineT : mpcq_engine {
     }
     return 0;
   }
-  int cmd_buf(size_t n) {
-    if (cmd_elems >= n) return 0;
-    if (d_cmd) { (void)hipFree(d_cmd); d_cmd = nullptr; cmd_elems = 0; }
-    HIP_TRY(hipMalloc((void**)&d_cmd, n * sizeof(double)));
-    cmd_elems = n;
-    return 0;
-  }
   int get_command(double* rotor, double* coll, double* rates) override {
     int rc;
-    if ((rc = cmd_buf((size_t)B * 8))) return rc;
-    hipLaunchKernelGGL(mpcq::command_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, stream, m, st.w, st.X, d_cmd, d_cmd + (size_t)B * 4, d_cmd + (size_t)B * 5, B);
+    HIP_TRY(d_cmd.grow((size_t)B * 8));
+    double* c = d_cmd.p;
+    hipLaunchKernelGGL(mpcq::command_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, stream, m, st.w, st.X, c, c + (size_t)B * 4, c + (size_t)B * 5, B);
     HIP_TRY(hipGetLastError());
-    if (rotor && (rc = d2h(rotor, d_cmd, (size_t)B * 4))) return rc;
-    if (coll && (rc = d2h(coll, d_cmd + (size_t)B * 4, (size_t)B))) return rc;
-    if (rates && (rc = d2h(rates, d_cmd + (size_t)B * 5, (size_t)B * 3))) return rc;
+    if (rotor && (rc = d2h(rotor, c, (size_t)B * 4))) return rc;
+    if (coll && (rc = d2h(coll, c + (size_t)B * 4, (size_t)B))) return rc;
+    if (rates && (rc = d2h(rates, c + (size_t)B * 5, (size_t)B * 3))) return rc;
     return 0;
   }
   int get_finished(int32_t* out) override {
@@ -990,11 +987,10 @@ struct EngineT : mpcq_engine {
   }
   int get_chunk(double* out) override {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_get_reference_chunk needs mpcq_set_trajectories first");
-    int rc;
-    if ((rc = cmd_buf((size_t)B * N * 13))) return rc;
-    hipLaunchKernelGGL(mpcq::chunk_kernel<T>, dim3(B), dim3(64), 0, stream, m, st.traj, st.tlen, st.idx, d_cmd);
+    HIP_TRY(d_cmd.grow((size_t)B * N * 13));
+    hipLaunchKernelGGL(mpcq::chunk_kernel<T>, dim3(B), dim3(64), 0, stream, m, st.traj, st.tlen, st.idx, d_cmd.p);
     HIP_TRY(hipGetLastError());
-    return d2h(out, d_cmd, (size_t)B * N * 13);
+    return d2h(out, d_cmd.p, (size_t)B * N * 13);
   }
   int sim_plant(const double* w, int n_sub, double sim_dt) override {
     int rc;
@@ -1145,11 +1141,12 @@ int mpcq_create_sized(const mpcq_config* c_in, uint64_t cfg_size, mpcq_engine** 
   if (c->nb) { e->basis.assign(c->basis, c->basis + 3 * c->nb); e->theta.assign(c->theta, c->theta + 9); }
   e->cfg.basis = nullptr; e->cfg.theta = nullptr;
   const int rc = e->init();
-  if (rc) { delete e; return rc; }
+  if (rc) { delete e; return rc; }   // (under `guard`)
   *out = e;
   return 0;
 }
-int mpcq_destroy(mpcq_engine* e) { delete e; return 0; }
+// (the guard outlives the destructors of the engine's members, which free its device memory)
+int mpcq_destroy(mpcq_engine* e) { if (!e) return 0; DeviceGuard guard(e->cfg.device); delete e; return 0; }
 // null check + the engine's device made current for the duration of the call
 #define ENTER(e) if (!(e)) return fail(MPCQ_ERR_INVALID, "null engine"); DeviceGuard guard_((e)->cfg.device)
 int mpcq_reset(mpcq_engine* e) { ENTER(e); return e->reset(); }
@@ -1286,13 +1283,41 @@ int mpcq_set_solver_state(mpcq_engine* e, const int32_t* qp_iter, const double* 
 
 // ---- continuous operation: trajectory slots (mpcq_replan.hpp)
 namespace {
-int rp_staging(mpcq_engine* e, size_t in_elems) {
-  if (e->rp_in_elems < in_elems) {
-    if (e->d_rp_in) { (void)hipFree(e->d_rp_in); e->d_rp_in = nullptr; e->rp_in_elems = 0; }
-    HIP_TRY(hipMalloc((void**)&e->d_rp_in, in_elems * sizeof(double)));
-    e->rp_in_elems = in_elems;
-  }
-  if (!e->d_rp_int) HIP_TRY(hipMalloc((void**)&e->d_rp_int, (size_t)3 * e->B * sizeof(int)));
+// What mpcq_replan and mpcq_replan_nonlinear (`who`) share: the argument and state checks, in the order a caller meets them, and the
+// inputs on the device.  limits_ok / limits_rule and opts_ok are the caller's own checks of v_max, a_max, dt and of its options.
+struct ReplanInputs {
+  TrajSlots t;
+  const double *wp, *start;   // waypoints [B,n_wp,3]; start points [B,start_stride]: the caller's [B,3] or the plant state
+  int start_stride;
+  const int* mask;            // nullptr: the quadrotors whose finished flag is set
+  int* code;                  // [B] result codes
+  double* extra;              // `extra` doubles of staging behind the inputs
+};
+int replan_inputs(const char* who_, mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, bool limits_ok, const char* limits_rule,
+                  int32_t derivative_to_optimize, bool opts_ok, const int32_t* mask, size_t extra, ReplanInputs& in) {
+  const std::string who(who_);
+  if (!wp) return fail(MPCQ_ERR_INVALID, who + ": null waypoints");
+  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
+  if (!limits_ok) return fail(MPCQ_ERR_INVALID, who + ": v_max, a_max and dt must be " + limits_rule);
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
+  if (!opts_ok) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
+  in.t = e->traj_slots();
+  if (!e->have_traj || !in.t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, who + " without start points needs mpcq_sim_reset first (the plant state)");
+  const size_t B = e->B, nwp = B * n_wp * 3;
+  HIP_TRY(e->d_rp_in.grow(nwp + B * 3 + extra));
+  HIP_TRY(e->d_rp_int.grow(3 * B));
+  double* d_in = e->d_rp_in.p;
+  int* d_int = e->d_rp_int.p;
+  HIP_TRY(hipMemcpyAsync(d_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (start) HIP_TRY(hipMemcpyAsync(d_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(d_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  in.wp = d_in;
+  in.start = start ? d_in + nwp : in.t.plant;
+  in.start_stride = start ? 3 : 13;
+  in.mask = mask ? d_int : nullptr;
+  in.code = d_int + B;
+  in.extra = d_in + nwp + B * 3;
   return 0;
 }
 }  // namespace
@@ -1300,25 +1325,13 @@ int rp_staging(mpcq_engine* e, size_t in_elems) {
 int mpcq_replan(mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize,
                 double dt, const int32_t* mask, int32_t* out) {
   ENTER(e);
-  if (!wp) return fail(MPCQ_ERR_INVALID, "mpcq_replan: null waypoints");
-  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, "mpcq_replan: n_wp outside 1..7");
-  if (!(v_max > 0) || !(a_max > 0) || !(dt > 0)) return fail(MPCQ_ERR_INVALID, "mpcq_replan: v_max, a_max and dt must be > 0");
-  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, "mpcq_replan: derivative_to_optimize outside 2..4");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replan needs mpcq_set_trajectories first");
-  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, "mpcq_replan without start points needs mpcq_sim_reset first (the plant state)");
-  const size_t B = e->B, nwp = B * n_wp * 3;
-  int rc;
-  if ((rc = rp_staging(e, nwp + B * 3))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->d_rp_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (start) HIP_TRY(hipMemcpyAsync(e->d_rp_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(e->d_rp_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  int* d_code = e->d_rp_int + B;
+  ReplanInputs in;
+  if (const int rc = replan_inputs("mpcq_replan", e, start, wp, n_wp, v_max > 0 && a_max > 0 && dt > 0, "> 0", derivative_to_optimize, true, mask, 0, in)) return rc;
+  const TrajSlots& t = in.t;
   hipLaunchKernelGGL(mpcq::replan::replan_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
-                     start ? (const double*)(e->d_rp_in + nwp) : t.plant, start ? 3 : 13, (const double*)e->d_rp_in, (int)n_wp, v_max, a_max,
-                     (int)derivative_to_optimize, dt, mask ? (const int*)e->d_rp_int : nullptr, d_code);
+                     in.start, in.start_stride, in.wp, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code);
   HIP_TRY(hipGetLastError());
-  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, in.code, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -1326,32 +1339,21 @@ int mpcq_replan(mpcq_engine* e, const double* start, const double* wp, int32_t n
 int mpcq_replan_nonlinear(mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize,
                           double dt, const int32_t* mask, int32_t* out, const mpcq_minsnap_nl_options* opts, double* info, double* pieces, double* d_free) {
   ENTER(e);
-  if (!wp) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: null waypoints");
-  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: n_wp outside 1..7");
-  if (!(v_max > 0) || !(a_max > 0) || !(dt > 0) || !std::isfinite(v_max) || !std::isfinite(a_max))
-    return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: v_max, a_max and dt must be finite and > 0");
-  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: derivative_to_optimize outside 2..4");
   const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
-  if (!mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, "mpcq_replan_nonlinear: options out of range");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replan_nonlinear needs mpcq_set_trajectories first");
-  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, "mpcq_replan_nonlinear without start points needs mpcq_sim_reset first (the plant state)");
-  const size_t B = e->B, nwp = B * n_wp * 3, n_info = B * 6, n_pc = B * n_wp * 33, n_df = B * (n_wp - 1) * 9;
-  int rc;
-  if ((rc = rp_staging(e, nwp + B * 3 + n_info + n_pc + n_df))) return rc;
-  double* d_info = e->d_rp_in + nwp + B * 3;
+  const size_t B = e->B, n_info = B * 6, n_pc = B * n_wp * 33, n_df = B * (n_wp - 1) * 9;   // (used behind the check of n_wp only)
+  ReplanInputs in;
+  if (const int rc = replan_inputs("mpcq_replan_nonlinear", e, start, wp, n_wp, v_max > 0 && a_max > 0 && dt > 0 && std::isfinite(v_max) && std::isfinite(a_max),
+                                   "finite and > 0", derivative_to_optimize, mpcq_nl::nl_opts_valid(o), mask, n_info + n_pc + n_df, in))
+    return rc;
+  const TrajSlots& t = in.t;
+  double* d_info = in.extra;
   double* d_pc = d_info + n_info;
   double* d_df = d_pc + n_pc;
-  HIP_TRY(hipMemcpyAsync(e->d_rp_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (start) HIP_TRY(hipMemcpyAsync(e->d_rp_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(e->d_rp_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  int* d_code = e->d_rp_int + B;
   hipLaunchKernelGGL(mpcq::replan::replan_nl_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::NlLds), e->stream, t.traj, t.Tmax, t.len, t.idx,
-                     t.finished, start ? (const double*)(e->d_rp_in + nwp) : t.plant, start ? 3 : 13, (const double*)e->d_rp_in, (int)n_wp, v_max,
-                     a_max, (int)derivative_to_optimize, dt, mask ? (const int*)e->d_rp_int : nullptr, d_code, o, info ? d_info : nullptr,
-                     pieces ? d_pc : nullptr, d_free && n_df ? d_df : nullptr);
+                     t.finished, in.start, in.start_stride, in.wp, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code, o,
+                     info ? d_info : nullptr, pieces ? d_pc : nullptr, d_free && n_df ? d_df : nullptr);
   HIP_TRY(hipGetLastError());
-  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, in.code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   if (info) HIP_TRY(hipMemcpyAsync(info, d_info, n_info * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (pieces) HIP_TRY(hipMemcpyAsync(pieces, d_pc, n_pc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (d_free && n_df) HIP_TRY(hipMemcpyAsync(d_free, d_df, n_df * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -1373,13 +1375,15 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
   }
   if (count == 0) return 0;
   const size_t rows = (size_t)count * t.Tmax * 13;
-  int rc;
-  if ((rc = rp_staging(e, rows))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->d_rp_in, traj, rows * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_rp_int, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->d_rp_int + e->B, len, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e->d_rp_in.grow(rows));
+  HIP_TRY(e->d_rp_int.grow((size_t)3 * e->B));
+  double* d_rows = e->d_rp_in.p;
+  int *d_idx = e->d_rp_int.p, *d_len = d_idx + e->B;
+  HIP_TRY(hipMemcpyAsync(d_rows, traj, rows * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(d_idx, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(d_len, len, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(mpcq::replan::install_kernel, dim3(count), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
-                     (const double*)e->d_rp_in, (const int*)e->d_rp_int, (const int*)(e->d_rp_int + e->B));
+                     (const double*)d_rows, (const int*)d_idx, (const int*)d_len);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
@@ -1409,33 +1413,27 @@ int mpcq_record_start(mpcq_engine* e, const int32_t* quads, int32_t count, int32
   std::sort(nr.sorted.begin(), nr.sorted.end());
   nr.pos.resize(n);
   for (int j = 0; j < n; ++j) nr.pos[j] = (int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), sel[j]) - nr.sorted.begin());
-  // the groups of mpcq_sim_steps (EngineT::sim_steps: the same `per`)
-  const int G = e->n_groups, per = ((e->B + G - 1) / G + 7) / 8 * 8;
-  for (int g = 0; g < G; ++g) {
-    const int g0 = std::min(e->B, g * per), g1 = std::min(e->B, g0 + per);
-    nr.glo.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g0) - nr.sorted.begin()));
-    nr.ghi.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g1) - nr.sorted.begin()));
+  for (const Group& g : e->groups) {   // the part of the selection inside every group of mpcq_sim_steps, and inside the whole batch
+    nr.glo.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g.b0) - nr.sorted.begin()));
+    nr.ghi.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g.b0 + g.n) - nr.sorted.begin()));
   }
-  auto alloc = [&](void** p, size_t bytes, const char* what) {
-    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) {
-      (void)hipGetLastError();
-      *p = nullptr;
-      return fail(MPCQ_ERR_DEVICE, std::string("mpcq_record_start: cannot allocate ") + std::to_string(bytes) + " bytes for " + what);
-    }
-    return 0;
+  // (a return from here on releases what `nr` holds by then; the engine's recorder is touched by the last statement only)
+  auto need = [](auto& buf, size_t elems, const char* what) {
+    if (buf.grow(elems) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(MPCQ_ERR_DEVICE, std::string("mpcq_record_start: cannot allocate ") + std::to_string(elems * sizeof(*buf.p)) + " bytes for " + what);
   };
-  int rc = alloc((void**)&nr.d_sel, (size_t)n * sizeof(int), "the selection");
+  int rc = need(nr.d_sel, (size_t)n, "the selection");
   for (int f = 0; f < mpcq::record::NF && !rc; ++f) {
     if (!(fields >> f & 1)) continue;
     const size_t elems = (size_t)capacity * n * mpcq::record::width(f, e->nb);
-    rc = f == mpcq::record::F_SOLVER ? alloc((void**)&nr.d_solver, elems * sizeof(int), "the solver field")
-                                     : alloc((void**)&nr.d_f[f], elems * sizeof(double), "a recorded field");
+    rc = f == mpcq::record::F_SOLVER ? need(nr.d_solver, elems, "the solver field") : need(nr.d_f[f], elems, "a recorded field");
   }
-  if (!rc && (fields & MPCQ_RECORD_DRAG)) rc = alloc((void**)&nr.d_snap, (size_t)n * mpcq::record::SNAP * sizeof(double), "the drag snapshot");
-  if (!rc && hipMemcpyAsync(nr.d_sel, nr.sorted.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream) != hipSuccess)
-    rc = fail(MPCQ_ERR_DEVICE, "mpcq_record_start: copy of the selection failed");
-  if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(MPCQ_ERR_DEVICE, "mpcq_record_start: hipStreamSynchronize failed");
-  if (rc) { nr.release(); return rc; }
+  if (!rc && (fields & MPCQ_RECORD_DRAG)) rc = need(nr.d_snap, (size_t)n * mpcq::record::SNAP, "the drag snapshot");
+  if (rc) return rc;
+  if (hipMemcpyAsync(nr.d_sel.p, nr.sorted.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    return fail(MPCQ_ERR_DEVICE, "mpcq_record_start: copy of the selection failed");
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(MPCQ_ERR_DEVICE, "mpcq_record_start: hipStreamSynchronize failed");
   nr.period_of.reserve(capacity < (1 << 20) ? capacity : (1 << 20));
   nr.on = true;
   r = std::move(nr);
@@ -1476,7 +1474,7 @@ int mpcq_record_get(mpcq_engine* e, int32_t field, double* out) {
   if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
   int f = 0;
   while (!(field >> f & 1)) ++f;
-  return rec_read(e, (const double*)r.d_f[f], mpcq::record::width(f, e->nb), out);
+  return rec_read(e, (const double*)r.d_f[f].p, mpcq::record::width(f, e->nb), out);
 }
 int mpcq_record_get_solver(mpcq_engine* e, int32_t* out) {
   ENTER(e);
@@ -1484,7 +1482,7 @@ int mpcq_record_get_solver(mpcq_engine* e, int32_t* out) {
   if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_get_solver: no active recording");
   if (!(r.fields & MPCQ_RECORD_SOLVER)) return fail(MPCQ_ERR_INVALID, "mpcq_record_get_solver: MPCQ_RECORD_SOLVER was not recorded");
   if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
-  return rec_read(e, (const int*)r.d_solver, 4, (int*)out);
+  return rec_read(e, (const int*)r.d_solver.p, 4, (int*)out);
 }
 int mpcq_record_get_periods(mpcq_engine* e, int64_t* out) {
   ENTER(e);
@@ -1505,7 +1503,7 @@ int mpcq_record_stop(mpcq_engine* e) {
   ENTER(e);
   if (!e->rec.on) return fail(MPCQ_ERR_STATE, "mpcq_record_stop: no active recording");
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the buffers)
-  e->rec.release();
+  e->rec = Recorder();
   return 0;
 }
 
@@ -1536,7 +1534,7 @@ int mpcq_record_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t row
   if (var && !fixed && !(r.fields & MPCQ_RECORD_RGP_C)) return fail(MPCQ_ERR_INVALID, "mpcq_record_predict: var needs MPCQ_RECORD_RGP_C in the recording");
   if (row0 < 0 || nrows < 1 || (long long)row0 + nrows > r.rows) return fail(MPCQ_ERR_INVALID, "mpcq_record_predict: row window outside the rows recorded so far");
   const int nb = e->nb;
-  return predict_run<double>(e, r.d_f[mpcq::record::F_MU], 3L * nb, fixed ? nullptr : r.d_f[mpcq::record::F_C], 3L * nb * nb, (size_t)r.count * nrows, r.pos.data(),
+  return predict_run<double>(e, r.d_f[mpcq::record::F_MU].p, 3L * nb, fixed ? nullptr : r.d_f[mpcq::record::F_C].p, 3L * nb * nb, (size_t)r.count * nrows, r.pos.data(),
                              row0, nrows, r.count, xq, M, 0, mean, var);
 }
 

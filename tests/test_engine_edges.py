@@ -450,6 +450,48 @@ def test_emu(case):
     case(EMU)
 
 
+def test_emu_engine_gives_back_what_it_took():
+    """close() releases every device and pinned allocation and every event the engine made, whichever entry points grew their scratch
+    buffers on the way and with a recording still active: the emulator's count of live allocations and events (mpcq_emu_live) is back
+    at its value from before the engine was created.  Two lockstep groups, both precisions."""
+    import ctypes
+    import gc
+    from mpc_quad_ros_amd.engine import RECORD_FIELDS, REPLAN_DONE
+    live = _lib.load(EMU).mpcq_emu_live
+    live.restype = ctypes.c_long
+    B, N, nb, M = 16, 5, 10, 7
+    hover = np.array([0, 0, 3.0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+    x0 = np.tile(hover, (B, 1)); x0[:, 0] = np.arange(B)
+    rng = np.random.default_rng(5)
+    for precision in (0, 1):
+        gc.collect()                                          # engines earlier tests left to the collector go now, not in between
+        before = live()
+        e = Engine(EngineConfig(batch=B, N=N, quad=hummingbird(), nb=nb, basis=rgp_basis_linspace(12.0, nb), precision=precision,
+                                tune=dict(groups=2)), lib_path=EMU)
+        assert e.get_groups() == 2 and live() > before
+        e.set_trajectories(np.tile(x0[:, None, :], (1, 300, 1)), np.full(B, 300))
+        e.sim_reset(x0)
+        e.record_start(fields=tuple(RECORD_FIELDS), capacity=8)
+        e.sim_steps(3, 2, 5e-3)
+        e.step(x0)
+        xq = np.tile(np.linspace(-3, 3, M), (3, 1))
+        e.rgp_predict(xq); e.rgp_predict(np.tile(xq, (B, 1, 1)), per_quad=True)
+        mean, var = e.record_predict(xq)
+        assert mean.shape == (B, 4, 3, M) and np.isfinite(mean).all() and np.isfinite(var).all()
+        mask = np.zeros(B, np.int32); mask[[1, 9]] = 1        # one quadrotor of either group
+        codes = e.replan(x0[:, None, 0:3] + rng.uniform(-1, 1, (B, 2, 3)), 12.0, 12.0, mask=mask)
+        assert (codes[mask == 1] == REPLAN_DONE).all(), codes
+        e.replace_trajectories([2, 12], np.tile(x0[[2, 12], None, :], (1, 300, 1)), [40, 50])
+        e.get_command(); e.get_reference_chunk()
+        e.record_stop()
+        e.set_trajectories(np.tile(x0[:, None, :], (1, 450, 1)))      # another Tmax: the slots are allocated anew
+        e.record_start(quads=[3, 11, 4], fields=("x_odom", "drag", "solver"), capacity=4)
+        e.sim_steps(2, 2, 5e-3)
+        assert e.record_info()[0] == 2
+        e.close()                                             # the second recording is still active
+        assert live() == before, (precision, live() - before)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=[c.__name__.strip("_") for c in CASES])
 def test_gpu(case):

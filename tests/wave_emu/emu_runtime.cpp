@@ -88,11 +88,14 @@ hipError_t hipGetDeviceCount(int* n) { *n = 8; return hipSuccess; }   // pretend
 static thread_local int emu_device = 0;
 hipError_t hipSetDevice(int d) { emu_device = d; return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = emu_device; return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : 2; }
-hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
+// what the library holds at the moment: device and pinned allocations and events (tests: an engine gives back all it took)
+static long emu_live = 0;
+extern "C" long mpcq_emu_live() { return emu_live; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = std::malloc(n ? n : 1); emu_live += *p != nullptr; return *p ? hipSuccess : 2; }
+hipError_t hipHostFree(void* p) { emu_live -= p != nullptr; std::free(p); return hipSuccess; }
 hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 256; return hipSuccess; }
-hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : 2; }
-hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); emu_live += *p != nullptr; return *p ? hipSuccess : 2; }
+hipError_t hipFree(void* p) { emu_live -= p != nullptr; std::free(p); return hipSuccess; }
 hipError_t hipMemset(void* p, int v, size_t n) { std::memset(p, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { std::memset(p, v, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
@@ -103,10 +106,10 @@ hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (void*)1; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = new emuEvent; return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new emuEvent; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = new emuEvent; ++emu_live; return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }   // (launches execute synchronously here)
-hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { emu_live -= e != nullptr; delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
