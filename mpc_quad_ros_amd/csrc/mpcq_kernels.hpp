@@ -44,52 +44,20 @@ namespace mpcq {
 // inlined copies, and the substage loop of the sensitivity pass likewise: the step executes every phase once per control
 // period, so straight-line code is fetched from L2 every time (18 % of the wave cycles waited for instructions with
 // everything unrolled); a loop body is fetched once and then runs from the instruction cache.
-#ifndef MPCQ_ROLL_RK
-#define MPCQ_ROLL_RK 1
-#endif
-// Round-6 restructurings of the glue between the phases: built, measured on the MI355X (tools/r6_ab.sh, tools/r6_ab4.sh,
-// profiles/r6_glue_ab.txt) and NOT in the product -- the step kernel sits at the edge of the register file (256 VGPRs, 160+ SGPR spills),
-// and what an edit saves in instructions the allocation it shifts gives back:
-//   MPCQ_G_SHFL = 1     GP sums of a stage's three lanes through ds_bpermute instead of LDS memory + two barriers      0 .. - 2 %
-//   MPCQ_G_DXBATCH = 1  gap operand of a working-set pass: the global loads of a block issued together                 0 .. - 2 %
-//   (tools/experiments/r6_glue_restructurings.patch:)  the new iterate kept in registers between the full step and the cost: - 7 %
-//   (20 KB more code, SGPR spills 190 -> 340); the compact fp64 layout without X in LDS -- 22.1 instead of 24.3 KB, SEVEN quadrotors
-//   per CU: + 0.5 %, a seventh resident wavefront buys nothing once the groups fill the launch tails; fused ratio-test / step passes: 0;
-//   the solver's previous-period record fetched with the load phase instead of in front of the QP: - 1 %.
-#ifndef MPCQ_G_SHFL
-#define MPCQ_G_SHFL 0
-#endif
-#ifndef MPCQ_G_DXBATCH
-#define MPCQ_G_DXBATCH 0
-#endif
-#if MPCQ_ROLL_RK
 #define MPCQ_RK_LOOP _Pragma("clang loop unroll(disable)")
-#else
-#define MPCQ_RK_LOOP _Pragma("unroll")
-#endif
-#ifndef MPCQ_ROLL_SENS
-#define MPCQ_ROLL_SENS 1
-#endif
-#if MPCQ_ROLL_SENS
 #define MPCQ_SENS_LOOP _Pragma("clang loop unroll(disable)")
-#else
-#define MPCQ_SENS_LOOP _Pragma("unroll")
-#endif
-// Phases of the step: inlined into the kernel by default; -DMPCQ_NOINLINE_PHASES keeps them as functions so that
-// tools/kernel_resources.sh can attribute the code size (measurement only).  MPCQ_COLD marks the phases only the
-// interior-point fallback uses: out of line, so that the many call sites of the fallback do not each carry a copy.
-#ifdef MPCQ_NOINLINE_PHASES
-#define MPCQ_PHASE __device__ __attribute__((noinline))
-#else
+// Round 6 built and measured several restructurings of the glue between the phases (cross-lane GP sums, batched gap loads, the new
+// iterate kept in registers, a compact fp64 layout, fused ratio-test / step passes, an earlier fetch of the solver's record); none was
+// adopted: the step kernel sits at the edge of the register file (256 VGPRs, 160+ SGPR spills), and what an edit saves in instructions
+// the allocation it shifts gives back.  Numbers: profiles/r6_glue_ab.txt; code: tools/experiments/r6_glue_restructurings.patch.
+// Markers of the phases of the step, both plain inline functions: MPCQ_PHASE a phase every step runs, MPCQ_COLD one that only the
+// interior-point fallback uses.  A label for the reader, not an outlining: everything is inlined into the kernel.
 #define MPCQ_PHASE __device__ inline
-#endif
-#ifndef MPCQ_COLD
 #define MPCQ_COLD __device__ inline
-#endif
 template <typename T> struct alignas(16) V4 { T a, b, c, d; };
 constexpr int NX = 13, NU = 4, NY = 17;
 
-extern __shared__ unsigned char smem_raw[];   // dynamic LDS (16-byte aligned base), shared by the kernels and their out-of-line phases
+extern __shared__ unsigned char smem_raw[];   // dynamic LDS (16-byte aligned base), shared by the kernels and their phases
 
 // ------------------------------------------------------------------ checked build (-DMPCQ_CHECKED, libmpcq_checked.so)
 // Diagnostic build for the GPU (AddressSanitizer is not available on the device here): every pointer of the step kernel
@@ -208,6 +176,26 @@ constexpr int SUBS = 4 * SUBW + 1;  // per-stage stride of the records (odd: lan
 enum : int { MODE_TRAJ = 1, MODE_POST = 2, MODE_RUN = 4, MODE_PLANT_FIRST = 8, MODE_STATIC_GP = 16 };
 // why a warm active-set attempt ended without a solution (field x 100000 of qp_iter; 0: it was not given up / there was none)
 enum : int { QPX_BUDGET = 1, QPX_PINS = 2, QPX_WRONG = 3, QPX_BOUNCE = 4, QPX_NUMERIC = 5, QPX_SKIPPED = 6 };
+// qp_iter (include/mpcq.h): what a QP solve returns and, as prev_iter, what the same quadrotor's next solve starts from (0: cold
+// start).  Decimal fields:
+//   passes + interior-point iterations | x 1000: the warm attempt was given up or skipped (fallback solve) |
+//   x 10000: flip mark | x 100000: why the warm attempt ended (QPX_*).
+// A quadrotor whose references are out of reach (inputs saturated over most of the horizon, the working set changing by
+// many inputs every period) fails the warm attempt period after period: after a fallback the next attempt is short
+// (warm_retry passes), so that such a quadrotor costs its launch one interior-point solve, not that plus a long
+// active-set attempt; the first period in which the short attempt succeeds restores the full budget.
+// Flip mark: the previous solve fell back AND its solution differed from the one before in more than flip_max
+// bound states -- a quadrotor whose saturated inputs flip between rotors from period to period (infeasible references,
+// near-degenerate QPs): the previous working set is no guess at all there, the warm attempt is skipped altogether.
+struct QpPrev { bool flipping; int warm_cap; };   // the flip mark of prev_iter ; the pass budget it leaves the warm attempt (0: skipped)
+template <typename M> __device__ inline QpPrev qp_prev(const M& m, const int prev_iter) {
+  const bool flipping = m.flip_max >= 0 && (prev_iter / 10000) % 10 != 0;
+  return {flipping, flipping ? 0 : ((prev_iter / 1000) % 10 != 0 ? m.warm_retry : m.warm_max)};
+}
+// count: iterations + passes (+ 1000 behind a fallback) ; chg: bound states that changed against the previous solution
+template <typename M> __device__ inline int qp_iter_pack(const M& m, const int count, const int chg, const int why) {
+  return count + (m.flip_max >= 0 && chg > m.flip_max ? 10000 : 0) + 100000 * why;
+}
 // MODE_STATIC_GP: the GP of the model is fixed (mpcq_config.flags & MPCQ_FLAG_STATIC_GP): the post phase skips the RGP update.
 // MODE_RUN: free-running closed loop, DevState::run_* periods per launch.  MODE_PLANT_FIRST: the launch starts by
 // advancing the plant state run_x with the previous launch's control (lockstep closed loop without a plant kernel
@@ -221,10 +209,7 @@ __device__ inline void pf_start(Prof& p) { p.t = __builtin_readcyclecounter(); }
 __device__ inline void pf_stop(Prof& p, int k) { const unsigned long long n = __builtin_readcyclecounter(); p.acc[k] += n - p.t; p.t = n; }
 #define PF_ARG , Prof& pf
 #define PF_PASS , pf
-#ifdef MPCQ_PROFILE_NOSTAMP
-#define PF_START()
-#define PF_STOP(k)
-#elif defined(MPCQ_PROFILE_OTHER)   // what lies BETWEEN the bracketed phases of the fp64 step, by bucket (slots 11..15; tools/profile_phases.py PROF_MODE=other)
+#ifdef MPCQ_PROFILE_OTHER   // what lies BETWEEN the bracketed phases of the fp64 step, by bucket (slots 11..15; tools/profile_phases.py PROF_MODE=other)
 #define PF_START() pf_stop(pf, pf.oth)
 #define PF_STOP(k) pf_stop(pf, k)
 #else
@@ -333,7 +318,7 @@ struct Lds {
   int AB, c, qv, r0, lb, ub, alpha, basis, wq;
   int z, sl, su, ll, lu, grad, vin, dza, dz, rho, act, rt, dx, Dx, K, Linv, sF, sT, stv;
   int sub, rgp, qtotal;
-  int gab, zb, gx, gtotal;   // stage data (AB'', c, qv) in global memory? ; LDS zero block ; GP exchange scratch (MPCQ_G_SHFL = 0 only) ; global elements per instance
+  int gab, zb, gx, gtotal;   // stage data (AB'', c, qv) in global memory? ; LDS zero block ; GP exchange scratch ; global elements per instance
   int gk;                    // Riccati gains K, Lambda^-1 in the global record as well, and r0 / lb / ub inside the union (written behind the shooting)
   int mrow;                  // multiplier rows (always global): per stage 4 rows [M_a(13) | F_uu row(4) | gt_a | pad 2]
   int pst;                   // cost-to-go of every stage (always global): [P_i as accumulator tile (256) | p_i (16)]
@@ -365,13 +350,13 @@ __host__ __device__ inline Lds lds_layout(int N, int nb, int gab, int mixed = 0)
     L.c = gtake(N * VS);
     L.qv = gtake((N + 1) * VS);
     L.zb = take(VS);
-    L.gx = MPCQ_G_SHFL ? 0 : take(22 * 8);   // 21 lane triples + the idle lane 63
+    L.gx = take(22 * 8);   // 21 lane triples + the idle lane 63
   } else {
     L.AB = take(N * ABS + VS);
     L.c = take(N * VS);
     L.qv = take((N + 1) * VS);
     L.zb = L.AB + N * ABS;
-    L.gx = L.AB;   // (MPCQ_G_SHFL = 0: exchange scratch of shoot_states; AB'' is not written before shoot_sens)
+    L.gx = L.AB;   // (exchange scratch of shoot_states; AB'' is not written before shoot_sens)
   }
   L.mrow = gtake(N * MROW * NU);
   L.pst = gtake(((N + PSTEP - 1) / PSTEP) * PST);   // one tile per PSTEP stages (pst_first)
@@ -569,9 +554,6 @@ __device__ inline void mfma(double (&acc)[4], double a, double b) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   d4 cc = {acc[0], acc[1], acc[2], acc[3]};
   cc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, cc, 0, 0, 0);
-#ifdef MPCQ_DGEMM_SETTLE
-  asm volatile("s_nop 15\n\ts_nop 15" : "+a"(cc));
-#endif
   acc[0] = cc[0]; acc[1] = cc[1]; acc[2] = cc[2]; acc[3] = cc[3];
 }
 #else
@@ -753,22 +735,12 @@ __device__ inline void model_eval(const QC<T>& m, int nb, const TG* L2inv, const
         s0 += k;
         s1 -= k * dlt;
       }
-#if MPCQ_G_SHFL
-      // the three lanes of a stage exchange their sums through the LDS crossbar (ds_bpermute: no LDS memory, no barrier; lane 63, which has
-      // no partners, reads lanes 0 / 1 and is not used)
-      const int l0 = lane_id() - gd;
-      const TG e0 = s0, e1 = s1 * l2;
-      CK_EXEC_FULL(5);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) { mg[d] = (T)__shfl(e0, l0 + d); mp[d] = (T)__shfl(e1, l0 + d); }
-#else
       gx[gd] = s0;
       gx[3 + gd] = s1 * l2;
       __syncthreads();
 #pragma unroll
       for (int d = 0; d < 3; ++d) { mg[d] = (T)gx[d]; mp[d] = (T)gx[3 + d]; }
       __syncthreads();
-#endif
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) f[7 + i] += R[3 * i] * mg[0] + R[3 * i + 1] * mg[1] + R[3 * i + 2] * mg[2];
@@ -896,18 +868,13 @@ template <typename C, typename M> __device__ inline int cNB(const M& m) { return
 // ------------------------------------------------------------------ shooting
 // pass 1: lane (triple) per interval, 4 RK substages in TQ; writes records + gap c_i = Phi_i - X_{i+1}
 // (the part X_i - X_{i+1} of the gap is formed in double)
-// TS: arithmetic of the integration.  The float instances integrate in double too (MPCQ_MIXED_SHOOT64) and round the RECORDS to
+// TS: arithmetic of the integration.  The float instances integrate in double too (ShootT<float>) and round the RECORDS to
 // float: their QP solution is refined against fp64 residuals of the stored stage data, so what is left of the 1e-4 budget goes to
 // the data themselves -- records computed in float carry ~1e-6 relative error, which a saturated quadrotor far off its reference
 // (gradient scale 3e4) turns into 2e-4 .. 7e-4 of control deviation; computed in double and rounded once it is the 6e-8 of the storage.
 // The GP sums stay in TQ (the exps of the basis): benign in float.
-#ifndef MPCQ_MIXED_SHOOT64
-#define MPCQ_MIXED_SHOOT64 1
-#endif
 template <typename TQ> struct ShootT { using T = TQ; };
-#if MPCQ_MIXED_SHOOT64
 template <> struct ShootT<float> { using T = double; };
-#endif
 template <typename C, typename TQ = typename C::T, bool GAB = C::GAB>
 MPCQ_PHASE void shoot_states(const DevModel<TQ>& m, P<double> D, P<TQ> S, P<TQ> A, const Lds& L, bool gp) {
   using TS = typename ShootT<TQ>::T;
@@ -916,7 +883,7 @@ MPCQ_PHASE void shoot_states(const DevModel<TQ>& m, P<double> D, P<TQ> S, P<TQ> 
   const TS h = (TS)m.h;
   // with the GP in the model the three axis sums (nb exps each) of a stage go to three neighbouring lanes
   const int per = gp ? 3 : 1, lanes_used = gp ? 63 : 64, spr = lanes_used / per;   // stages per round
-  P<TQ> gx = S + (L.gx + (lane / 3) * 8);   // LDS exchange scratch (MPCQ_G_SHFL = 0 only)
+  P<TQ> gx = S + (L.gx + (lane / 3) * 8);   // LDS exchange scratch
   for (int base = 0; base < N; base += spr) {
     const int il = lane / per, d = lane - il * per;
     const bool valid = lane < lanes_used && base + il < N;
@@ -1010,12 +977,8 @@ MPCQ_PHASE void shoot_sens(const DevModel<TQ>& m, P<TQ> S, P<TQ> A, const Lds& L
   // idle near zero (N = 50, bench workload: worst deviation 9.5e-6 against 2.0e-6 of full thrust).  What is left is the float STORAGE of
   // AB'' (6e-8 relative): keeping what the float gaps and cost gradients drop of their double values as a second float, read by the
   // double sweeps only, was measured and changed nothing (7.8e-5 against 9.2e-5 of an idling quadrotor's own largest control) at 5-10 % of
-  // the speed.  -DMPCQ_MIXED_SENS32: this pass in float (2-3 % faster).
-#ifdef MPCQ_MIXED_SENS32
-  shoot_sens_t<C, TQ, TQ>(m, S, A, L, cN<C>(m));
-#else
+  // the speed.  (The pass in float would be 2-3 % faster.)
   shoot_sens_t<C, typename ShootT<TQ>::T, TQ>(m, S, A, L, cN<C>(m));
-#endif
 }
 
 // ------------------------------------------------------------------ QP: vector sweeps
@@ -1554,11 +1517,7 @@ template <typename TQ, typename PT> __device__ inline void dbg_dump(const DevMod
 // The gradient follows an interior-point step without an adjoint sweep (H dz = -rho - Sigma dz elementwise) in both precisions.  In float
 // the residual of the float solve piles up in it (which is why it was re-swept every iteration until round 5) -- but all the mixed-precision
 // method needs from the interior point is the working set, which it then checks against double residuals: one sweep of four less per
-// iteration, +2 % on the lockstep rate, the soaks as clean as before (-DMPCQ_F32_IPM_INCR=0: the gradient sweep per iteration).
-#ifndef MPCQ_F32_IPM_INCR
-#define MPCQ_F32_IPM_INCR 1
-#endif
-template <typename TQ> __device__ constexpr bool IPM_INCR() { return sizeof(TQ) == 8 || MPCQ_F32_IPM_INCR != 0; }
+// iteration, +2 % on the lockstep rate, the soaks as clean as before.
 template <typename C, typename TQ = typename C::T, bool GAB = C::GAB, typename M = DevModel<TQ>, typename PA = P<TQ>>
 MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, const TQ tol, const TQ gm, int& it PF_ARG, const TQ rd_floor = TQ(3e-4), const int cap = 0) {
   constexpr int N = C::N > 0 ? C::N : 1, nv = N * NU, R = (nv + 63) / 64;
@@ -1661,23 +1620,18 @@ MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, co
 #endif
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      // fp64: the gradient follows the step without a sweep (see ipm_run)
-      if (IPM_INCR<TQ>()) g[r] += ap * (-rho[r] - (ll[r] * rsl[r] + lu[r] * rsu[r]) * d[r]);
+      // the gradient follows the step without a sweep (see ipm_run)
+      g[r] += ap * (-rho[r] - (ll[r] * rsl[r] + lu[r] * rsu[r]) * d[r]);
       sl[r] = sl[r] + ap * d[r]; su[r] = su[r] - ap * d[r];
       ll[r] = ll[r] + ad * dl[r]; lu[r] = lu[r] + ad * du[r];
       if (on[r]) {
         S[L.z + ix[r]] += ap * d[r]; S[L.sl + ix[r]] = sl[r]; S[L.su + ix[r]] = su[r];
         S[L.ll + ix[r]] = ll[r]; S[L.lu + ix[r]] = lu[r];
-        if (IPM_INCR<TQ>()) S[L.grad + gi[r]] = g[r];
+        S[L.grad + gi[r]] = g[r];
       }
     }
     for (int i = tid; i < (N + 1) * VS; i += 64) S[L.dx + i] += ap * S[L.Dx + i];
     __syncthreads();
-    if constexpr (!IPM_INCR<TQ>()) {
-      PF_START(); adjoint<C, TQ, GAB>(m, S, A, L); PF_STOP(PF_ADJ);
-#pragma unroll
-      for (int r = 0; r < R; ++r) g[r] = S[L.grad + gi[r]];
-    }
   }
   return status;
 }
@@ -1772,15 +1726,14 @@ MPCQ_COLD int ipm_run(const DevModel<TQ>& m, P<TQ> S, P<TQ> A, P<TQ> Kb, const L
       const TQ dl = S[L.act + i], du = S[L.rt + i];
       S[L.z + i] += ap * d; S[L.sl + i] = sl + ap * d; S[L.su + i] = su - ap * d;
       S[L.ll + i] = ll + ad * dl; S[L.lu + i] = lu + ad * du;
-      // fp64: the gradient follows the step without a sweep.  The corrector solved (H + Sigma) dz = -rho with
+      // The gradient follows the step without a sweep.  The corrector solved (H + Sigma) dz = -rho with
       // Sigma = ll/sl + lu/su of this iteration, so H dz = -rho - Sigma dz elementwise (the solve leaves a residual at the
       // rounding level of double, far below the hand-over tolerance; the active-set iterations that follow recompute
-      // everything).  fp32 keeps the adjoint sweep: there the residual of the solve would pile up in the gradient.
-      if (IPM_INCR<TQ>()) S[L.grad + GI(i)] += ap * (-S[L.rho + i] - (ll * trcp(sl) + lu * trcp(su)) * d);
+      // everything; in float the residual piles up in the gradient, which the mixed-precision method tolerates: see ipm_run_regs).
+      S[L.grad + GI(i)] += ap * (-S[L.rho + i] - (ll * trcp(sl) + lu * trcp(su)) * d);
     }
     for (int i = tid; i < (N + 1) * VS; i += 64) S[L.dx + i] += ap * S[L.Dx + i];
     __syncthreads();
-    if (!IPM_INCR<TQ>()) { PF_START(); adjoint<C>(m, S, A, L); PF_STOP(PF_ADJ); }
   }
   return status;
 }
@@ -1853,33 +1806,8 @@ MPCQ_PHASE bool polish(const DevModel<TQ>& m, P<TQ> S, P<TQ> A, P<TQ> G, const L
           if (S[L.act + i] != TQ(0) || tmin(-S[L.lb + i], S[L.ub + i]) < TQ(0.1)) hi = i >> 2;   // (ascending i per lane: the last hit is the highest)
         ptop = wave_max(hi);
         keep_p = ptop >= 0;
-#ifdef MPCQ_AB_NO_PSTORE   // A/B measurement only: no cost-to-go tiles, every factorisation starts at the last stage
-        keep_p = false;
-#endif
       }
       __syncthreads();
-#if MPCQ_G_DXBATCH
-      // (the gaps come from the stage records -- global memory in the GAB layouts: the loads of a block are issued together, one memory
-      //  round trip per block instead of one per 64 elements; the pad slots 13..15 of c are zero, shoot_sens)
-      constexpr int CB = 5;
-      for (int base = 0; base < N * VS; base += 64 * CB) {
-        TQ cv[CB];
-#pragma unroll
-        for (int u = 0; u < CB; ++u) { const int it = base + 64 * u + tid; cv[u] = A[L.c + (it < N * VS ? it : 0)]; }
-#pragma unroll
-        for (int u = 0; u < CB; ++u) {
-          const int it = base + 64 * u + tid, i = it >> 4, r = it & 15;
-          if (it >= N * VS) continue;
-          TQ v = cv[u];
-          if (nact > 0 && r < NX) {
-#pragma unroll
-            for (int j = 0; j < NU; ++j)
-              if (S[L.act + i * NU + j] != TQ(0)) v += A[L.AB + i * ABS + r * ABW + 10 + j] * S[L.z + i * NU + j];
-          }
-          S[L.Dx + it] = v;
-        }
-      }
-#else
       for (int it = tid; it < N * VS; it += 64) {
         const int i = it >> 4, r = it & 15;
         TQ v = 0;
@@ -1893,7 +1821,6 @@ MPCQ_PHASE bool polish(const DevModel<TQ>& m, P<TQ> S, P<TQ> A, P<TQ> G, const L
         }
         S[L.Dx + it] = v;
       }
-#endif
       __syncthreads();
       PF_START();
       TQ gfac = 0;
@@ -2694,19 +2621,9 @@ MPCQ_PHASE int solve_qp(const DevModel<TQ>& m, P<double> D, P<TQ> S, P<TQ> A, P<
   TQ gm = 1;
   const P<TQ> Kb = C::GK ? G : S;   // where the gains live
   static_assert(sizeof(TQ) == 8, "float instances solve their QP in solve_qp_mixed");
-  // prev_iter: this quadrotor's previous return value (0: cold start).  Decimal fields (qp_iter of include/mpcq.h):
-  //   passes + interior-point iterations | x 1000: the warm attempt was given up or skipped (fallback solve) |
-  //   x 10000: flip mark | x 100000: why the warm attempt ended (QPX_*).
-  // A quadrotor whose references are out of reach (inputs saturated over most of the horizon, the working set changing by
-  // many inputs every period) fails the warm attempt period after period: after a fallback the next attempt is short
-  // (warm_retry passes), so that such a quadrotor costs its launch one interior-point solve, not that plus a long
-  // active-set attempt; the first period in which the short attempt succeeds restores the full budget.
-  // Flip mark: the previous solve fell back AND its solution differed from the one before in more than flip_max
-  // bound states -- a quadrotor whose saturated inputs flip between rotors from period to period (infeasible references,
-  // near-degenerate QPs): the previous working set is no guess at all there, the warm attempt is skipped altogether.
-  const bool flipping = m.flip_max >= 0 && (prev_iter / 10000) % 10 != 0;
-  const int warm_cap = flipping ? 0 : ((prev_iter / 1000) % 10 != 0 ? m.warm_retry : m.warm_max);
-  if (flipping) { wpasses = 1000; why = QPX_SKIPPED; }   // counts as a fallback solve
+  const QpPrev prev = qp_prev(m, prev_iter);   // (prev_iter: this quadrotor's previous return value, see qp_iter)
+  const int warm_cap = prev.warm_cap;
+  if (prev.flipping) { wpasses = 1000; why = QPX_SKIPPED; }   // counts as a fallback solve
   if (prev_iter > 0 && warm_cap > 0) {
     if (polish<C>(m, S, A, G, L, gm, wpasses, true, warm_cap, why PF_PASS)) {   // sets z = 0 and its own gradient scale
       *status = 0;
@@ -2789,7 +2706,7 @@ MPCQ_PHASE int solve_qp(const DevModel<TQ>& m, P<double> D, P<TQ> S, P<TQ> A, P<
     const unsigned sweeps = (unsigned)(wp + passes + 3 * it + 2 + (need_roll ? 1 : 0) + (broke ? 2 : 0));
     *work = (int)((unsigned)(it + passes + wp) | (broke ? 0x8000u : 0u) | ((sweeps < 2047u ? sweeps : 2047u) << 16) | ((unsigned)(fit < 31 ? fit : 31) << 27));
   }
-  return it + passes + wpasses + (m.flip_max >= 0 && chg > m.flip_max ? 10000 : 0) + 100000 * why;
+  return qp_iter_pack(m, it + passes + wpasses, chg, why);
 }
 
 // Box-QP solve of the float instances (mixed precision).  Same three stages as solve_qp -- (0) warm active-set attempt, (1) interior
@@ -2806,9 +2723,9 @@ MPCQ_PHASE int solve_qp_mixed(const DevModel<float>& m, P<double> D, P<float> S,
   int it = 0, passes = 0, wpasses = 0, why = 0, conv = 1, st = 0;
   TQ gm = 1;
   const P<TQ> Kb = C::GK ? G : S;
-  const bool flipping = m.flip_max >= 0 && (prev_iter / 10000) % 10 != 0;   // (prev_iter, flip mark, budgets: see solve_qp)
-  const int warm_cap = flipping ? 0 : ((prev_iter / 1000) % 10 != 0 ? m.warm_retry : m.warm_max);
-  if (flipping) { wpasses = 1000; why = QPX_SKIPPED; }
+  const QpPrev prev = qp_prev(m, prev_iter);
+  const int warm_cap = prev.warm_cap;
+  if (prev.flipping) { wpasses = 1000; why = QPX_SKIPPED; }
   bool solved = false, ipm_sound = true;
   for (int stage = (prev_iter > 0 && warm_cap > 0) ? 0 : 1; stage <= 2 && !solved && ipm_sound; ++stage) {
     int cap = warm_cap;
@@ -2874,7 +2791,7 @@ MPCQ_PHASE int solve_qp_mixed(const DevModel<float>& m, P<double> D, P<float> S,
     const int wp = wpasses % 1000;
     *work = (it + passes + wp) | ((2 * (wp + passes) + 4 * it + 2) << 16);
   }
-  return it + passes + wpasses + (m.flip_max >= 0 && chg > m.flip_max ? 10000 : 0) + 100000 * why;
+  return qp_iter_pack(m, it + passes + wpasses, chg, why);
 }
 
 // ------------------------------------------------------------------ RGP regress (3 axes, one new point each)
