@@ -148,7 +148,8 @@ const char* mpcq_last_error(void);
 /* "mpcq <major.minor[.patch]> (gfx950, source <16 hex digits>+<8 hex digits>)": the 16 digits are the hash of the sources and the build
  * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
  * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
- * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp) and, since 0.6.3, the flight recorder (csrc/mpcq_record.hpp). */
+ * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp), since 0.6.3 the flight recorder (csrc/mpcq_record.hpp), since 0.6.4 the RGP
+ * read-out (csrc/mpcq_predict.hpp) and, since 0.6.5, the device missions (csrc/mpcq_mission.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -359,6 +360,40 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx /*[count]*/, in
 /* The trajectory buffer and lengths as they are now.  A checkpoint after replans restores with mpcq_set_trajectories(traj, len),
  * then mpcq_set_state(idx = ...) and mpcq_set_solver_state(finished = ...). */
 int mpcq_get_trajectories(mpcq_engine* e, double* traj /*[B,Tmax,13] or NULL*/, int32_t* len /*[B] or NULL*/);
+
+/* ---- device missions (since 0.6.5): the node requests the next flight in the callback that sees the finish
+ * (src/mpc_controller_node.py:372-399); here a queue of upcoming flights per quadrotor lives on the device and a launch behind every
+ * period installs the next one for whoever just finished, with no host round trip.  A period is what the flight recorder counts: one
+ * mpcq_step / mpcq_step_device_async call, one iteration of mpcq_sim_steps / mpcq_sim_control_periods; mpcq_solve is not a period.
+ * Per quadrotor, behind every period: if its finished flag is set and leg[b] < L, a flight is planned through [start, wp[b, leg[b]]] --
+ * exactly what mpcq_replan (nonlinear = 0) or mpcq_replan_nonlinear (nonlinear = 1, options opts) would plan -- and installed as they
+ * install it (rows, padding, length, cursor 0, flag 0).  start is the plant position behind that period's plant update
+ * (mpcq_sim_steps / mpcq_sim_control_periods) or the period's measurement x_meas[b, 0:3] (mpcq_step, mpcq_step_device_async): the start
+ * points a host loop `sim_steps(1); replan(mask = finished & (leg < L))` passes, and the results are bit for bit that loop's.  The leg
+ * is consumed whatever the MPCQ_REPLAN_* code: a negative code leaves trajectory, cursor and flag as they were and the next period
+ * tries the next leg.  A quadrotor whose queue is exhausted (leg[b] == L) holds its last reference row, as without a mission.
+ * On the stream of a period the order is: recorder snapshot -> ordering launch -> step -> recorder row -> plant -> mission; a recorded
+ * row of the finishing period shows finished = 1 and the old cursor, the next row cursor 0 of the new flight.  While a mission is
+ * active every plant update of mpcq_sim_steps is a launch of its own (same arithmetic, same results as the fused form).
+ * mpcq_sim_run (one persistent launch) flies no mission: MPCQ_ERR_STATE while one is active.  Host calls of mpcq_replan* and
+ * mpcq_replace_trajectories stay legal and consume no legs.  With no mission set every launch sequence and result is what it was.
+ *
+ * mpcq_mission_set uploads the queue wp [B,L,n_wp,3] and the leg counters leg0 [B] (NULL: 0; values 0..L -- a checkpoint restores with
+ * the leg of mpcq_mission_get) and resets the log and the period count; calling it again replaces the queue.  MPCQ_ERR_INVALID: wp NULL,
+ * n_wp outside 1..7, L < 1, v_max / a_max / dt not finite and > 0, derivative_to_optimize outside 2..4, nonlinear not 0 / 1, options
+ * outside the rules of include/mpcq_nl_options.h, leg0 outside 0..L.  MPCQ_ERR_STATE before mpcq_set_trajectories. */
+int mpcq_mission_set(mpcq_engine* e, const double* wp /*[B,L,n_wp,3]*/, int32_t L, int32_t n_wp, double v_max, double a_max,
+                     int32_t derivative_to_optimize, double dt, int32_t nonlinear, const mpcq_minsnap_nl_options* opts /*or NULL*/,
+                     const int32_t* leg0 /*[B] or NULL*/);
+/* The mission's state, behind everything the engine has enqueued; every pointer may be NULL.  leg [B]: legs consumed so far;
+ * installed [B]: flights installed; last_code [B]: code of the last consumed leg (MPCQ_REPLAN_SKIPPED: none yet); leg_code [B,L]: code
+ * of every leg (MPCQ_REPLAN_SKIPPED: not consumed); leg_period [B,L]: the period number since mpcq_mission_set in which the leg was
+ * consumed, -1 if it has not been; info [B,6] (nonlinear: the info row of mpcq_replan_nonlinear for the last installed flight, NaN
+ * before the first; linear: NaN).  MPCQ_ERR_STATE: no mission set. */
+int mpcq_mission_get(mpcq_engine* e, int32_t* leg /*[B]*/, int32_t* installed /*[B]*/, int32_t* last_code /*[B]*/,
+                     int32_t* leg_code /*[B,L]*/, int32_t* leg_period /*[B,L]*/, double* info /*[B,6]*/);
+/* Mission off, the queue freed: period launches are exactly what they are without one.  MPCQ_ERR_STATE: no mission set. */
+int mpcq_mission_stop(mpcq_engine* e);
 
 /* ---- flight recorder (since 0.6.3): per-period logs of a swarm that flies on the device (the reference appends one row per control
  * step, src/mpc_controller_node.py:353-364, src/execute_trajectory.py:269-275).  A period is one fused step of every quadrotor: one

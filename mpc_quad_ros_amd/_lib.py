@@ -98,6 +98,10 @@ SYMBOLS = [
                                              _ip, _np, _dp, _dp, _dp]),
     ("mpcq_replace_trajectories", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _dp, _ip]),
     ("mpcq_get_trajectories", ctypes.c_int, [_vp, _dp, _ip]),
+    ("mpcq_mission_set", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                        ctypes.c_int32, _np, _ip]),
+    ("mpcq_mission_get", ctypes.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _dp]),
+    ("mpcq_mission_stop", ctypes.c_int, [_vp]),
     ("mpcq_record_start", ctypes.c_int, [_vp, _ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     ("mpcq_record_info", ctypes.c_int, [_vp, _ip, _lp, _lp]),
     ("mpcq_record_get", ctypes.c_int, [_vp, ctypes.c_int32, _dp]),

@@ -23,6 +23,7 @@
 #include "mpcq_kernels.hpp"
 #include "mpcq_replan.hpp"
 #include "mpcq_replan_nl.hpp"
+#include "mpcq_mission.hpp"
 #include "mpcq_record.hpp"
 #include "mpcq_predict.hpp"
 
@@ -211,6 +212,18 @@ struct Recorder {
   DevBuf<int> d_solver;                  // [capacity][count][4]
   DevBuf<double> d_snap;                 // [count][SNAP]: x_pred_prev and has_prev in front of the step (MPCQ_RECORD_DRAG)
 };
+// A device mission (mpcq_mission_*, mpcq_mission.hpp): the queue of upcoming flights, the per-quadrotor leg counters and the log of consumed
+// legs on the device, and what every flight is planned with.  The launch behind a period is mission_launch.
+struct Mission {
+  bool on = false;
+  int L = 0, n_wp = 0, order = 0, nonlinear = 0;
+  double v_max = 0, a_max = 0, dt = 0;
+  mpcq_nl::Opts opts;
+  long long periods = 0;   // periods issued since mpcq_mission_set
+  DevBuf<double> d_wp;     // [B,L,n_wp,3]
+  DevBuf<double> d_info;   // [B,6] (nonlinear)
+  DevBuf<int> d_int;       // leg [B] | installed [B] | last_code [B] | claim [B] | leg_code [B,L] | leg_period [B,L]
+};
 // Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
 // on a stream of its own, the event that marks the end of its part of a call.
 struct Group {
@@ -260,6 +273,8 @@ struct mpcq_engine : EngineQueues {
   DevBuf<double> d_rp_in;        // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
   DevBuf<int> d_rp_int;          // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
+  Mission ms;                    // mpcq_mission_set .. mpcq_mission_stop
+  int mission_next_period() { return ms.on ? (int)ms.periods++ : -1; }   // the number of the period about to be issued (-1: no mission)
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
   std::vector<double> kxinv64;
   struct PredictScratch {
@@ -361,6 +376,30 @@ int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long 
   if (var) HIP_TRY(hipMemcpyAsync(var, a.var, no * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return 0;
+}
+
+// The mission launch of one period (number `period` since mpcq_mission_set) for the quadrotors [b0, b0 + n) on stream s, behind everything
+// the period has issued there.  start [B,13]: where the flights begin (the plant state behind its update, or the period's measurement).
+void mission_launch(mpcq_engine* e, hipStream_t s, int b0, int n, const double* start, int period) {
+  namespace rp = mpcq::replan;
+  const Mission& ms = e->ms;
+  const TrajSlots t = e->traj_slots();
+  const size_t B = e->B;
+  rp::MissionArgs a;
+  a.traj = t.traj; a.Tmax = t.Tmax; a.lens = t.len; a.idx = t.idx; a.finished = t.finished;
+  a.start = start; a.wp = ms.d_wp.p;
+  a.L = ms.L; a.n_wp = ms.n_wp; a.order = ms.order;
+  a.v_max = ms.v_max; a.a_max = ms.a_max; a.dt = ms.dt;
+  a.b0 = b0; a.n = n; a.period = period;
+  int* d = ms.d_int.p;
+  a.leg = d; a.installed = d + B; a.last_code = d + 2 * B; a.claim = d + 3 * B;
+  a.leg_code = d + 4 * B; a.leg_period = a.leg_code + B * ms.L;
+  a.info = ms.nonlinear ? ms.d_info.p : nullptr;
+  const mpcq_nl::Opts o = ms.opts;
+  if (ms.nonlinear)
+    hipLaunchKernelGGL(rp::mission_kernel<rp::NlLds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::NlLds>), s, a, o);
+  else
+    hipLaunchKernelGGL(rp::mission_kernel<rp::Lds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::Lds>), s, a, o);
 }
 
 template <typename T>
@@ -773,9 +812,10 @@ struct EngineT : mpcq_engine {
   }
   // One period of groups[gi], the only place that issues one.  On the group's stream, in this order: the recorder's snapshot (row >= 0:
   // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the plant kernel
-  // (plant: s.run_nsub substeps of s.run_dt on s.run_x).  Every event is optional.  The caller asks hipGetLastError once it has issued
-  // all it has to issue.
-  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
+  // (plant: s.run_nsub substeps of s.run_dt on s.run_x) -> the mission launch (mper >= 0: a mission is active and this is its period
+  // number; the flights start at the plant state behind its update, or without a plant at the period's measurement).  Every event is
+  // optional.  The caller asks hipGetLastError once it has issued all it has to issue.
+  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
     const Group& g = groups[gi];
     if (g.n <= 0) return 0;
     if (row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
@@ -785,13 +825,14 @@ struct EngineT : mpcq_engine {
     if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
     if (plant)
       hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g.n + 63) / 64), dim3(64), 0, g.stream, m, s.run_x + (size_t)g.b0 * 13, st.w + (size_t)g.b0 * 4, s.run_nsub, s.run_dt, g.n);
+    if (mper >= 0) mission_launch(this, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, mper);
     return 0;
   }
   int solve(const double* x0) override {
     int rc;
     if ((rc = h2d(d_xin, x0, (size_t)B * 13))) return rc;
     st.x_meas = d_xin;
-    if ((rc = period(n_groups, st, 0, -1, ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, 0, -1, -1, ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -858,7 +899,7 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemcpyAsync(d_xin, h_pin, nx * sizeof(double), hipMemcpyHostToDevice, stream));
     st.x_meas = d_xin;
     int rc;
-    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipMemcpyAsync(h_pin + nx, st.w, nw * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -874,7 +915,7 @@ struct EngineT : mpcq_engine {
     s2.x_meas = d_x;
     s2.w_ext = d_w;   // the engine's own control record st.w is written as well (mpcq_get_command, mpcq_sim_plant_period(w = NULL))
     int rc;
-    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     return chk_after();   // (synchronises in the checked build only)
@@ -895,7 +936,9 @@ struct EngineT : mpcq_engine {
     // The plant update between two control periods rides at the head of the next step launch (MODE_PLANT_FIRST), where
     // it overlaps that launch's global loads; only the update after the last period needs the plant kernel.  Streaming batches
     // (split_plant, see create): every update is a launch of the plant kernel.  Same arithmetic, same results either way.
-    const bool split = split_plant;
+    // An active mission plans from the plant state behind the period's update, so it needs that update in front of its launch: every
+    // update is a launch then, too.
+    const bool split = split_plant || ms.on;
     s2.run_x = d_xs; s2.run_steps = 1; s2.run_nsub = n_sub; s2.run_dt = sim_dt;
     // Groups (see init): the K periods {order, step, plant} of a group go to its stream, issued period by period round the groups so that
     // the host feeds every queue.  The group streams start behind everything issued on the engine's stream and the engine's stream
@@ -907,10 +950,11 @@ struct EngineT : mpcq_engine {
     int rc;
     for (int k = 0; k < K; ++k) {
       const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of a group cover the selection inside it)
+      const int mper = mission_next_period();
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
       for (int g = 0; g < G; ++g) {
         hipEvent_t* pair = g == 0 && k % stride == 0 ? &kev[2 * (k / stride)] : nullptr;
-        if ((rc = period(g, s2, mode, row, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
+        if ((rc = period(g, s2, mode, row, mper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
       }
     }
     for (int g = 1; g < G; ++g) {
@@ -935,6 +979,7 @@ struct EngineT : mpcq_engine {
   int sim_run(int K, int n_sub, double sim_dt) override {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_run needs mpcq_set_trajectories first");
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
+    if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
     if (K <= 0) return 0;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
@@ -1082,9 +1127,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.4 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.5 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.4 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.5 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1386,6 +1431,73 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
                      (const double*)d_rows, (const int*)d_idx, (const int*)d_len);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+// ---- device missions (mpcq_mission.hpp; the launch: mission_launch, behind every period of EngineT::period)
+int mpcq_mission_set(mpcq_engine* e, const double* wp, int32_t L, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize, double dt,
+                     int32_t nonlinear, const mpcq_minsnap_nl_options* opts, const int32_t* leg0) {
+  ENTER(e);
+  const std::string who("mpcq_mission_set");
+  // (the checks of replan_inputs, in its order, plus those of the queue)
+  if (!wp) return fail(MPCQ_ERR_INVALID, who + ": null waypoints");
+  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
+  if (L < 1) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
+  if (nonlinear != 0 && nonlinear != 1) return fail(MPCQ_ERR_INVALID, who + ": nonlinear must be 0 or 1");
+  if (!(v_max > 0 && a_max > 0 && dt > 0 && std::isfinite(v_max) && std::isfinite(a_max) && std::isfinite(dt)))
+    return fail(MPCQ_ERR_INVALID, who + ": v_max, a_max and dt must be finite and > 0");
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
+  const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
+  if (nonlinear && !mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
+  const size_t B = e->B, nl = B * (size_t)L;
+  if (nl * n_wp * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  if (leg0)
+    for (size_t b = 0; b < B; ++b)
+      if (leg0[b] < 0 || leg0[b] > L) return fail(MPCQ_ERR_INVALID, who + ": leg0 outside 0..L");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still read the queue that is replaced)
+  Mission& ms = e->ms;
+  ms.on = false;
+  HIP_TRY(ms.d_wp.grow(nl * n_wp * 3));
+  HIP_TRY(ms.d_int.grow(4 * B + 2 * nl));
+  if (nonlinear) HIP_TRY(ms.d_info.grow(B * 6));
+  std::vector<int> h(4 * B + 2 * nl, 0);   // leg | installed | last_code | claim | leg_code | leg_period
+  for (size_t b = 0; b < B; ++b) { h[b] = leg0 ? leg0[b] : 0; h[2 * B + b] = MPCQ_REPLAN_SKIPPED; }
+  for (size_t k = 0; k < nl; ++k) { h[4 * B + k] = MPCQ_REPLAN_SKIPPED; h[4 * B + nl + k] = -1; }
+  HIP_TRY(hipMemcpyAsync(ms.d_wp.p, wp, nl * n_wp * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(ms.d_int.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  const std::vector<double> nan(nonlinear ? B * 6 : 0, std::nan(""));   // (info: NaN rows until a flight is installed)
+  if (nonlinear) HIP_TRY(hipMemcpyAsync(ms.d_info.p, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  ms.L = L; ms.n_wp = n_wp; ms.order = derivative_to_optimize; ms.nonlinear = nonlinear;
+  ms.v_max = v_max; ms.a_max = a_max; ms.dt = dt; ms.opts = o;
+  ms.periods = 0;
+  ms.on = true;
+  return 0;
+}
+int mpcq_mission_get(mpcq_engine* e, int32_t* leg, int32_t* installed, int32_t* last_code, int32_t* leg_code, int32_t* leg_period, double* info) {
+  ENTER(e);
+  const Mission& ms = e->ms;
+  if (!ms.on) return fail(MPCQ_ERR_STATE, "mpcq_mission_get: no mission set");
+  const size_t B = e->B, nl = B * (size_t)ms.L;
+  const int* d = ms.d_int.p;
+  if (leg) HIP_TRY(hipMemcpyAsync(leg, d, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (installed) HIP_TRY(hipMemcpyAsync(installed, d + B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (last_code) HIP_TRY(hipMemcpyAsync(last_code, d + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (leg_code) HIP_TRY(hipMemcpyAsync(leg_code, d + 4 * B, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (leg_period) HIP_TRY(hipMemcpyAsync(leg_period, d + 4 * B + nl, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (info && ms.nonlinear) HIP_TRY(hipMemcpyAsync(info, ms.d_info.p, B * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (info && !ms.nonlinear)
+    for (size_t k = 0; k < B * 6; ++k) info[k] = std::nan("");
+  return 0;
+}
+int mpcq_mission_stop(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->ms.on) return fail(MPCQ_ERR_STATE, "mpcq_mission_stop: no mission set");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the queue)
+  e->ms = Mission();
   return 0;
 }
 

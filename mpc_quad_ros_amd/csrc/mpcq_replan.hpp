@@ -219,25 +219,56 @@ __device__ inline void slot_commit(Lds& S, double* traj, int Tmax, int b, int le
 
 __device__ inline bool finite3(const double* p) { return __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]); }
 
-// One workgroup (one wavefront) per quadrotor.  start: [B,3] or the plant state [B,13] (start_stride 13); mask: [B] or NULL (the
-// finished flags select).  code [B]: MPCQ_REPLAN_*.
-__global__ __launch_bounds__(64) void replan_kernel(double* traj, int Tmax, int* lens, int* idx, int* finished, const double* start, int start_stride,
-                                                    const double* wp, int n_wp, double v_max, double a_max, int order, double dt,
-                                                    const int* mask, int* code) {
-#pragma clang fp contract(off)
-  Lds& S = *reinterpret_cast<Lds*>(smem_raw);
-  const int b = blockIdx.x, lane = threadIdx.x, n = n_wp + 1, ns = n_wp;
-  const bool sel = mask ? mask[b] != 0 : finished[b] != 0;
-  if (!sel) { if (lane == 0) code[b] = SKIPPED; return; }
+// Vertices of quadrotor b into S.V: the start point p0 [3], then its n_wp waypoints wp_b [n_wp,3].  False if one is not finite
+// (wave-uniform).  Starts with a barrier, so that a workgroup may plan one quadrotor after another in the same LDS.
+__device__ inline bool load_vertices(Lds& S, const double* p0, const double* wp_b, int n_wp) {
+  const int lane = threadIdx.x, n = n_wp + 1;
+  __syncthreads();
   if (lane < n) {
-    const double* p = lane == 0 ? start + (size_t)b * start_stride : wp + ((size_t)b * n_wp + lane - 1) * 3;
+    const double* p = lane == 0 ? p0 : wp_b + (size_t)(lane - 1) * 3;
     for (int k = 0; k < 3; ++k) S.V[lane][k] = p[k];
   }
   if (lane == 0) S.flag = 0;
   __syncthreads();
   if (lane < n && !finite3(S.V[lane])) S.flag = 1;
   __syncthreads();
-  if (S.flag) { if (lane == 0) code[b] = BAD_INPUT; return; }
+  return S.flag == 0;
+}
+
+// Rows [0, rows) of slot b from the pieces in S.coef with the segment ends in S.ends (mpcq_minsnap_sample: one lane per row, the host's
+// piece lookup, Horner order and 6-decimal rounding), then the install (slot_commit).
+__device__ inline void sample_install(Lds& S, double* traj, int Tmax, int* lens, int* idx, int* finished, int b, int ns, int rows, double dt) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x;
+  double* slot = traj + (size_t)b * Tmax * NX;
+  for (int k = lane; k < rows; k += 64) {
+    const double t = k * dt;
+    int seg = 0;
+    while (seg < ns - 1 && !(t < S.ends[seg])) ++seg;
+    const double tl = t - (seg > 0 ? S.ends[seg - 1] : 0.0);
+    double row[NX];
+    for (int i = 0; i < NX; ++i) row[i] = 0.0;
+    row[3] = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      const double* c = S.coef[seg][a];
+      double p = 0.0, v = 0.0;
+      for (int i = 0; i < 8; ++i) p = p * tl + c[7 - i];
+      for (int i = 0; i < 7; ++i) v = v * tl + (7 - i) * c[7 - i];
+      row[a] = rint(p * 1e6) / 1e6;
+      row[7 + a] = rint(v * 1e6) / 1e6;
+    }
+    for (int i = 0; i < NX; ++i) slot[(size_t)k * NX + i] = row[i];
+  }
+  slot_commit(S, traj, Tmax, b, rows, lens, idx, finished);
+}
+
+// The flight of one quadrotor, by the wavefront that calls it: planned through [p0, wp_b[0..n_wp)] and, on DONE, installed in slot b.
+// Returns the MPCQ_REPLAN_* code (wave-uniform).  Shared by replan_kernel (a host call) and mission_kernel (mpcq_mission.hpp, behind a period).
+__device__ inline int plan_linear(Lds& S, double* traj, int Tmax, int* lens, int* idx, int* finished, int b, const double* p0, const double* wp_b,
+                                  int n_wp, double v_max, double a_max, int order, double dt) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x, n = n_wp + 1, ns = n_wp;
+  if (!load_vertices(S, p0, wp_b, n_wp)) return BAD_INPUT;
   // segment-time estimate (mpcq_minsnap_estimate_times)
   if (lane < ns) {
     double d2 = 0;
@@ -265,38 +296,32 @@ __global__ __launch_bounds__(64) void replan_kernel(double* traj, int Tmax, int*
       }
     ok = viol(hi) <= 1.0;   // (leaves the pieces of `hi` in S.coef)
   }
-  if (!ok) { if (lane == 0) code[b] = LIMITS; return; }
+  if (!ok) return LIMITS;
   // sampling (mpcq_minsnap_sample): durations T[s] = T0[s] hi
   double total = 0;
   for (int s = 0; s < ns; ++s) total = total + S.T[s];
   const int rows = (int)ceil(total / dt);
-  if (rows > Tmax) { if (lane == 0) code[b] = TOO_LONG; return; }
+  if (rows > Tmax) return TOO_LONG;
   if (lane == 0) {
     double e = 0;
     for (int s = 0; s < ns; ++s) { e = e + S.T[s]; S.ends[s] = e; }
   }
   __syncthreads();
-  double* slot = traj + (size_t)b * Tmax * NX;
-  for (int k = lane; k < rows; k += 64) {
-    const double t = k * dt;
-    int seg = 0;
-    while (seg < ns - 1 && !(t < S.ends[seg])) ++seg;
-    const double tl = t - (seg > 0 ? S.ends[seg - 1] : 0.0);
-    double row[NX];
-    for (int i = 0; i < NX; ++i) row[i] = 0.0;
-    row[3] = 1.0;
-    for (int a = 0; a < 3; ++a) {
-      const double* c = S.coef[seg][a];
-      double p = 0.0, v = 0.0;
-      for (int i = 0; i < 8; ++i) p = p * tl + c[7 - i];
-      for (int i = 0; i < 7; ++i) v = v * tl + (7 - i) * c[7 - i];
-      row[a] = rint(p * 1e6) / 1e6;
-      row[7 + a] = rint(v * 1e6) / 1e6;
-    }
-    for (int i = 0; i < NX; ++i) slot[(size_t)k * NX + i] = row[i];
-  }
-  slot_commit(S, traj, Tmax, b, rows, lens, idx, finished);
-  if (lane == 0) code[b] = DONE;
+  sample_install(S, traj, Tmax, lens, idx, finished, b, ns, rows, dt);
+  return DONE;
+}
+
+// One workgroup (one wavefront) per quadrotor.  start: [B,3] or the plant state [B,13] (start_stride 13); mask: [B] or NULL (the
+// finished flags select).  code [B]: MPCQ_REPLAN_*.
+__global__ __launch_bounds__(64) void replan_kernel(double* traj, int Tmax, int* lens, int* idx, int* finished, const double* start, int start_stride,
+                                                    const double* wp, int n_wp, double v_max, double a_max, int order, double dt,
+                                                    const int* mask, int* code) {
+  Lds& S = *reinterpret_cast<Lds*>(smem_raw);
+  const int b = blockIdx.x;
+  const bool sel = mask ? mask[b] != 0 : finished[b] != 0;
+  int c = SKIPPED;
+  if (sel) c = plan_linear(S, traj, Tmax, lens, idx, finished, b, start + (size_t)b * start_stride, wp + (size_t)b * n_wp * 3, n_wp, v_max, a_max, order, dt);
+  if (threadIdx.x == 0) code[b] = c;
 }
 
 // mpcq_replace_trajectories: host-made rows stage [count, Tmax, 13] into the slots sel[0..count)

@@ -55,43 +55,33 @@ __device__ inline double nl_evaluate(NlLds& L, const double* x, int n, int order
   return mpcq_nl::nl_total(L.q, ns, x, o, vm, am, v_max, a_max, nullptr);
 }
 
-// One workgroup (one wavefront) per quadrotor, arguments as replan_kernel plus the options and the optional outputs info [B,6],
-// pieces [B,n_wp,33], d_free [B,n_wp-1,3,3] (NaN rows for quadrotors without a new flight).
-__global__ __launch_bounds__(64) void replan_nl_kernel(double* traj, int Tmax, int* lens, int* idx, int* finished, const double* start, int start_stride,
-                                                       const double* wp, int n_wp, double v_max, double a_max, int order, double dt,
-                                                       const int* mask, int* code, mpcq_nl::Opts o, double* info, double* pieces, double* dfree) {
+// The nonlinear flight of one quadrotor, by the wavefront that calls it: planned through [p0, wp_b[0..n_wp)] and, on DONE, installed in slot b.
+// Returns the MPCQ_REPLAN_* code (wave-uniform).  Optional outputs of this quadrotor: info [6], pieces [n_wp,33], dfree [n_wp-1,3,3] (NaN
+// unless a flight was made).  Shared by replan_nl_kernel (a host call) and mission_kernel (mpcq_mission.hpp, behind a period).
+__device__ inline int plan_nonlinear(NlLds& L, double* traj, int Tmax, int* lens, int* idx, int* finished, int b, const double* p0, const double* wp_b,
+                                     int n_wp, double v_max, double a_max, int order, double dt, const mpcq_nl::Opts& o, double* info, double* pieces,
+                                     double* dfree) {
 #pragma clang fp contract(off)
-  NlLds& L = *reinterpret_cast<NlLds*>(smem_raw);
   Lds& S = L.base;
-  const int b = blockIdx.x, lane = threadIdx.x, n = n_wp + 1, ns = n_wp, nv = ns + 9 * (n - 2);
-  auto finish = [&](int c, bool outputs) {   // result code; NaN outputs unless a flight was installed
-    if (lane == 0) code[b] = c;
-    if (outputs) return;
+  const int lane = threadIdx.x, n = n_wp + 1, ns = n_wp, nv = ns + 9 * (n - 2);
+  auto finish = [&](int c, bool outputs) {   // result code; NaN outputs unless a flight was made
+    if (outputs) return c;
     const double nan = __builtin_nan("");
-    if (info && lane < 6) info[(size_t)b * 6 + lane] = nan;
+    if (info && lane < 6) info[lane] = nan;
     if (pieces)
-      for (int e = lane; e < ns * 33; e += 64) pieces[(size_t)b * ns * 33 + e] = nan;
+      for (int e = lane; e < ns * 33; e += 64) pieces[e] = nan;
     if (dfree)
-      for (int e = lane; e < 9 * (n - 2); e += 64) dfree[(size_t)b * 9 * (n - 2) + e] = nan;
+      for (int e = lane; e < 9 * (n - 2); e += 64) dfree[e] = nan;
+    return c;
   };
-  const bool sel = mask ? mask[b] != 0 : finished[b] != 0;
-  if (!sel) { finish(SKIPPED, false); return; }
-  if (lane < n) {
-    const double* p = lane == 0 ? start + (size_t)b * start_stride : wp + ((size_t)b * n_wp + lane - 1) * 3;
-    for (int k = 0; k < 3; ++k) S.V[lane][k] = p[k];
-  }
-  if (lane == 0) S.flag = 0;
-  __syncthreads();
-  if (lane < n && !finite3(S.V[lane])) S.flag = 1;
-  __syncthreads();
-  if (S.flag) { finish(BAD_INPUT, false); return; }
+  if (!load_vertices(S, p0, wp_b, n_wp)) return finish(BAD_INPUT, false);
   // the linear stage: Nfabian times (shared nl_exp) raised to 0.1 s, the free derivatives that minimise J_d there
   if (lane < ns) S.T[lane] = mpcq_nl::nl_estimate_time(S.V, lane, v_max, a_max);
   unit_forms(S, order);   // (its barriers publish T)
   double total0 = 0;      // a linear stage longer than MAX_START_DURATION is refused (bounds every evaluation's work; the host's -3)
   for (int s = 0; s < ns; ++s) total0 = total0 + S.T[s];
-  if (!(total0 <= mpcq_nl::MAX_START_DURATION)) { finish(LIMITS, false); return; }
-  if (!solve_pieces(S, n, order)) { finish(-2, false); return; }
+  if (!(total0 <= mpcq_nl::MAX_START_DURATION)) return finish(LIMITS, false);
+  if (!solve_pieces(S, n, order)) return finish(-2, false);
   if (lane == 0) {
     mpcq_nl::Sbx& X = L.sbx;
     double* x0 = X.xt;   // (staging: sbx_init copies it into X.x before X.xt is written again)
@@ -119,46 +109,53 @@ __global__ __launch_bounds__(64) void replan_nl_kernel(double* traj, int Tmax, i
   double total = 0;
   for (int s = 0; s < ns; ++s) total = total + x[s];
   if (info && lane == 0) {
-    double* r = info + (size_t)b * 6;
+    double* r = info;
     r[0] = L.sbx.f0; r[1] = L.sbx.f; r[2] = L.sbx.nev; r[3] = total; r[4] = vpk; r[5] = apk;
   }
   if (pieces)
     for (int e = lane; e < ns * 33; e += 64) {
       const int s = e / 33, c = e - s * 33;
-      pieces[(size_t)b * ns * 33 + e] = c == 0 ? x[s] : (c < 25 ? S.coef[s][(c - 1) / NC][(c - 1) % NC] : 0.0);
+      pieces[e] = c == 0 ? x[s] : (c < 25 ? S.coef[s][(c - 1) / NC][(c - 1) % NC] : 0.0);
     }
   if (dfree)
-    for (int e = lane; e < 9 * (n - 2); e += 64) dfree[(size_t)b * 9 * (n - 2) + e] = x[ns + e];
+    for (int e = lane; e < 9 * (n - 2); e += 64) dfree[e] = x[ns + e];
   // sampling (mpcq_minsnap_sample) and install, as replan_kernel
   const double q = ceil(total / dt);   // (compared before the conversion: total / dt need not fit an int)
-  if (!(q <= (double)Tmax)) { finish(TOO_LONG, true); return; }
+  if (!(q <= (double)Tmax)) return finish(TOO_LONG, true);
   const int rows = (int)q;
   if (lane == 0) {
     double e = 0;
     for (int s = 0; s < ns; ++s) { e = e + x[s]; S.ends[s] = e; }
   }
   __syncthreads();
-  double* slot = traj + (size_t)b * Tmax * NX;
-  for (int k = lane; k < rows; k += 64) {
-    const double t = k * dt;
-    int seg = 0;
-    while (seg < ns - 1 && !(t < S.ends[seg])) ++seg;
-    const double tl = t - (seg > 0 ? S.ends[seg - 1] : 0.0);
-    double row[NX];
-    for (int i = 0; i < NX; ++i) row[i] = 0.0;
-    row[3] = 1.0;
-    for (int a = 0; a < 3; ++a) {
-      const double* c = S.coef[seg][a];
-      double p = 0.0, v = 0.0;
-      for (int i = 0; i < 8; ++i) p = p * tl + c[7 - i];
-      for (int i = 0; i < 7; ++i) v = v * tl + (7 - i) * c[7 - i];
-      row[a] = rint(p * 1e6) / 1e6;
-      row[7 + a] = rint(v * 1e6) / 1e6;
-    }
-    for (int i = 0; i < NX; ++i) slot[(size_t)k * NX + i] = row[i];
+  sample_install(S, traj, Tmax, lens, idx, finished, b, ns, rows, dt);
+  return finish(DONE, true);
+}
+
+// One workgroup (one wavefront) per quadrotor, arguments as replan_kernel plus the options and the optional outputs info [B,6],
+// pieces [B,n_wp,33], d_free [B,n_wp-1,3,3] (NaN rows for quadrotors without a new flight).
+__global__ __launch_bounds__(64) void replan_nl_kernel(double* traj, int Tmax, int* lens, int* idx, int* finished, const double* start, int start_stride,
+                                                       const double* wp, int n_wp, double v_max, double a_max, int order, double dt,
+                                                       const int* mask, int* code, mpcq_nl::Opts o, double* info, double* pieces, double* dfree) {
+  NlLds& L = *reinterpret_cast<NlLds*>(smem_raw);
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double* info_b = info ? info + (size_t)b * 6 : nullptr;
+  double* pieces_b = pieces ? pieces + (size_t)b * n_wp * 33 : nullptr;
+  double* dfree_b = dfree ? dfree + (size_t)b * 9 * (n_wp - 1) : nullptr;
+  const bool sel = mask ? mask[b] != 0 : finished[b] != 0;
+  int c = SKIPPED;
+  if (sel)
+    c = plan_nonlinear(L, traj, Tmax, lens, idx, finished, b, start + (size_t)b * start_stride, wp + (size_t)b * n_wp * 3, n_wp, v_max, a_max, order, dt, o,
+                       info_b, pieces_b, dfree_b);
+  else {   // NaN rows
+    const double nan = __builtin_nan("");
+    if (info_b && lane < 6) info_b[lane] = nan;
+    if (pieces_b)
+      for (int e = lane; e < n_wp * 33; e += 64) pieces_b[e] = nan;
+    if (dfree_b)
+      for (int e = lane; e < 9 * (n_wp - 1); e += 64) dfree_b[e] = nan;
   }
-  slot_commit(S, traj, Tmax, b, rows, lens, idx, finished);
-  finish(DONE, true);
+  if (lane == 0) code[b] = c;
 }
 
 }  // namespace replan

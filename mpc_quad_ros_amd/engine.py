@@ -153,6 +153,39 @@ class Engine:
         self._check(self.lib.mpcq_get_trajectories(self.h, _lib.d(traj), _lib.i(lengths)))
         return traj, lengths
 
+    # ---- device missions: a queue of upcoming flights per quadrotor, the next one installed on the device in the period a flight ends
+    def mission_set(self, wp, v_max, a_max, order=4, dt=0.01, nonlinear=False, opts=None, leg0=None):
+        """Queue wp [B, L, n_wp, 3]: behind every period (sim_steps, sim_control_periods, step, step_device_async) a quadrotor whose
+        finished flag is set and that has a leg left gets the flight replan (nonlinear: replan_nonlinear with `opts`) would plan from
+        where it stands through wp[b, leg[b]], without a host round trip.  leg0 [B]: the leg counters to start from (a checkpoint's
+        mission_get()["leg"]; None: 0).  Calling it again replaces the queue and resets the log."""
+        wp = self._f(wp)
+        if wp.ndim != 4 or wp.shape[0] != self.B or wp.shape[3] != 3:
+            raise ValueError(f"wp must be [B={self.B}, L, n_wp, 3]")
+        leg0 = None if leg0 is None else np.ascontiguousarray(leg0, dtype=np.int32).reshape(self.B)
+        o = _lib.nl_options(opts) if nonlinear else None
+        self._check(self.lib.mpcq_mission_set(self.h, _lib.d(wp), wp.shape[1], wp.shape[2], float(v_max), float(a_max), int(order), float(dt),
+                                              int(bool(nonlinear)), None if o is None else ctypes.byref(o), _lib.i(leg0)))
+        self._mission_legs = wp.shape[1]
+
+    def mission_get(self):
+        """The mission's state: leg [B] (legs consumed), installed [B] (flights installed), last_code [B], leg_code [B, L] (REPLAN_*;
+        REPLAN_SKIPPED: not consumed), leg_period [B, L] (period number since mission_set in which the leg was consumed, -1: not yet),
+        info [B, 6] (nonlinear: replan_nonlinear's info of the last installed flight; else NaN)."""
+        L = getattr(self, "_mission_legs", None)
+        if L is None:
+            raise _lib.MpcqError("mission_get needs mission_set first")
+        B = self.B
+        out = dict(leg=np.zeros(B, np.int32), installed=np.zeros(B, np.int32), last_code=np.zeros(B, np.int32),
+                   leg_code=np.zeros((B, L), np.int32), leg_period=np.zeros((B, L), np.int32), info=np.zeros((B, 6)))
+        self._check(self.lib.mpcq_mission_get(self.h, _lib.i(out["leg"]), _lib.i(out["installed"]), _lib.i(out["last_code"]),
+                                              _lib.i(out["leg_code"]), _lib.i(out["leg_period"]), _lib.d(out["info"])))
+        return out
+
+    def mission_stop(self):
+        self._check(self.lib.mpcq_mission_stop(self.h))
+        self._mission_legs = None
+
     # ---- flight recorder: per-period rows of selected quadrotors written on the device, read once
     def record_start(self, quads=None, fields=RECORD_DEFAULT, every=1, capacity=1000):
         """Record quadrotors `quads` (None: all, else indices in the order record_get returns them) from the next period on: the fields

@@ -291,6 +291,13 @@ def flight_waypoints(seed: int, index: int, leg: int, num_waypoints: int = 3, **
     return random_waypoints([int(seed), 7919 * (int(leg) + 1)], index, num_waypoints=num_waypoints, **kw)[1:]
 
 
+def mission_waypoints(seed: int, first_index: int, count: int, legs: int, num_waypoints: int = 3, **kw):
+    """The queue of a device mission (Engine.mission_set), [count, legs, num_waypoints, 3]: entry [i, l] is
+    flight_waypoints(seed, first_index + i, l), so the swarm flies through the same random waypoints as minsnap_mission's."""
+    return np.array([[flight_waypoints(seed, first_index + i, leg, num_waypoints, **kw) for leg in range(legs)] for i in range(count)]
+                    ).reshape(count, legs, num_waypoints, 3)
+
+
 def _mission_chunk(args):
     """Worker: missions of a contiguous index block, as float32-free compact rows (positions and velocities; the other
     columns of a reference are constants)."""
