@@ -149,7 +149,8 @@ const char* mpcq_last_error(void);
  * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
  * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
  * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp), since 0.6.3 the flight recorder (csrc/mpcq_record.hpp), since 0.6.4 the RGP
- * read-out (csrc/mpcq_predict.hpp) and, since 0.6.5, the device missions (csrc/mpcq_mission.hpp). */
+ * read-out (csrc/mpcq_predict.hpp), since 0.6.5 the device missions (csrc/mpcq_mission.hpp) and, since 0.6.6, the device circle generator
+ * (csrc/mpcq_circle.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -353,7 +354,24 @@ int mpcq_replan_nonlinear(mpcq_engine* e, const double* start /*[B,3] or NULL*/,
                           double v_max, double a_max, int32_t derivative_to_optimize, double dt,
                           const int32_t* mask /*[B] or NULL*/, int32_t* out /*[B] or NULL*/, const mpcq_minsnap_nl_options* opts /*or NULL*/,
                           double* info /*[B,6] or NULL*/, double* pieces /*[B,n_wp,33] or NULL*/, double* d_free /*[B,n_wp-1,3,3] or NULL*/);
-/* The same slot install for host-made rows (the reference's 'circle' / 'line' requests): quadrotors idx[0..count), rows
+/* Since 0.6.6.  The reference's 'circle' request (src/mpc_controller_node.py:430-453 -> sample_circle_trajectory_acc_dec(radius, v_max,
+ * dt, start_point)) generated on the device, one wavefront per selected quadrotor: the closed-form circle flights of the reference's
+ * TrajectoryGenerator (src/trajectory_generation/TrajectoryGenerator.py:41-131), a circle of radius[b] that starts at start_b and is
+ * flown in the x-y plane at the start's height, q = [1,0,0,0], body rates 0, positions / velocities rounded to 6 decimals. */
+#define MPCQ_CIRCLE_ACC_DEC 0       /* one round: angular speed up to v_max / radius at half time, then down again (the node's request) */
+#define MPCQ_CIRCLE_CONSTANT 1      /* one round at v_max */
+#define MPCQ_CIRCLE_ACCELERATING 2  /* t_max seconds, angular speed 0 -> v_max / radius -> 0 on a raised cosine */
+/* The row count is that of the reference (ceil(stop / dt), `stop` formed by its expression in double) and the running sums of angular
+ * speed and angle are accumulated in row order, so a flight differs from the host's trajectories.circle_trajectory by the device's
+ * sin / cos only: at most one quantum of the 6-decimal rounding, in rare entries.  radius [B], v_max [B]: per quadrotor; t_max is read for
+ * MPCQ_CIRCLE_ACCELERATING only.  Selection (mask / finished flags), start (NULL: the plant position), install and `out` as mpcq_replan.
+ * Codes: MPCQ_REPLAN_BAD_INPUT: start, radius or v_max not finite, or radius / v_max not > 0; MPCQ_REPLAN_TOO_LONG: more rows than Tmax;
+ * a negative code leaves trajectory, cursor and finished flag as they were.  MPCQ_ERR_INVALID: radius or v_max NULL, unknown kind, dt
+ * (MPCQ_CIRCLE_ACCELERATING: or t_max) not finite and > 0; MPCQ_ERR_STATE as mpcq_replan. */
+int mpcq_replan_circle(mpcq_engine* e, const double* start /*[B,3] or NULL*/, const double* radius /*[B]*/, const double* v_max /*[B]*/,
+                       int32_t kind, double dt, double t_max /*ACCELERATING only*/, const int32_t* mask /*[B] or NULL*/,
+                       int32_t* out /*[B] or NULL*/);
+/* The same slot install for host-made rows (the reference's 'line' request, or any other flight): quadrotors idx[0..count), rows
  * traj [count, Tmax, 13] of which the first len[j] are used; 1 <= len <= Tmax, indices in range and unique. */
 int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx /*[count]*/, int32_t count,
                               const double* traj /*[count,Tmax,13]*/, const int32_t* len /*[count]*/);
@@ -385,6 +403,21 @@ int mpcq_get_trajectories(mpcq_engine* e, double* traj /*[B,Tmax,13] or NULL*/, 
 int mpcq_mission_set(mpcq_engine* e, const double* wp /*[B,L,n_wp,3]*/, int32_t L, int32_t n_wp, double v_max, double a_max,
                      int32_t derivative_to_optimize, double dt, int32_t nonlinear, const mpcq_minsnap_nl_options* opts /*or NULL*/,
                      const int32_t* leg0 /*[B] or NULL*/);
+/* Since 0.6.6: a kind and limits per leg.  The reference sends v_max / a_max with every request and one of its request types is a circle;
+ * here quadrotor b flies leg l as legs[b, l] says, so a sweep over the limits is one batch.  mpcq_mission_set is the special case in
+ * which every leg is MPCQ_LEG_WAYPOINTS with that call's v_max / a_max. */
+#define MPCQ_LEG_WAYPOINTS 0   /* min-snap through wp[b, leg] (linear or nonlinear as the mission says) */
+#define MPCQ_LEG_CIRCLE    1   /* MPCQ_CIRCLE_ACC_DEC of `radius` at `v_max` from where the quadrotor stands */
+typedef struct mpcq_leg { int32_t kind, reserved; double v_max, a_max, radius; } mpcq_leg;
+/* legs [B,L] is uploaded once; everything else (claiming, leg consumption, the log, mpcq_mission_get / mpcq_mission_stop, the start
+ * point, dt) is mpcq_mission_set's.  A waypoint leg is planned through wp[b, leg] with its own v_max / a_max (radius is not read), a
+ * circle leg is what mpcq_replan_circle(MPCQ_CIRCLE_ACC_DEC, radius, v_max, dt) installs (a_max is checked, not used; wp[b, leg] is not
+ * read); info is NaN after a circle leg.  wp may be NULL if no leg is a waypoint leg (n_wp is not read then).  MPCQ_ERR_INVALID: legs
+ * NULL, an unknown kind, reserved != 0, a waypoint leg with wp NULL, v_max / a_max of any leg or the radius of a circle leg not finite
+ * and > 0, and the rules of mpcq_mission_set for L, n_wp (with wp), dt, derivative_to_optimize, nonlinear, opts and leg0. */
+int mpcq_mission_set_legs(mpcq_engine* e, const mpcq_leg* legs /*[B,L]*/, const double* wp /*[B,L,n_wp,3]; NULL iff no waypoint leg*/,
+                          int32_t L, int32_t n_wp, int32_t derivative_to_optimize, double dt, int32_t nonlinear,
+                          const mpcq_minsnap_nl_options* opts /*or NULL*/, const int32_t* leg0 /*[B] or NULL*/);
 /* The mission's state, behind everything the engine has enqueued; every pointer may be NULL.  leg [B]: legs consumed so far;
  * installed [B]: flights installed; last_code [B]: code of the last consumed leg (MPCQ_REPLAN_SKIPPED: none yet); leg_code [B,L]: code
  * of every leg (MPCQ_REPLAN_SKIPPED: not consumed); leg_period [B,L]: the period number since mpcq_mission_set in which the leg was

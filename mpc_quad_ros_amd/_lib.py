@@ -43,6 +43,15 @@ def nl_options(opts=None):
 
 _np = ctypes.POINTER(NlOptions)
 
+
+class Leg(ctypes.Structure):
+    """mpcq_leg (include/mpcq.h): kind, limits and radius of one leg of a device mission (mpcq_mission_set_legs)."""
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("v_max", ctypes.c_double), ("a_max", ctypes.c_double),
+                ("radius", ctypes.c_double)]
+
+
+_legp = ctypes.POINTER(Leg)
+
 # every symbol declared in include/mpcq.h: (name, restype, argtypes)
 SYMBOLS = [
     ("mpcq_last_error", ctypes.c_char_p, []),
@@ -96,10 +105,13 @@ SYMBOLS = [
     ("mpcq_replan", ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, _ip, _ip]),
     ("mpcq_replan_nonlinear", ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, _ip,
                                              _ip, _np, _dp, _dp, _dp]),
+    ("mpcq_replan_circle", ctypes.c_int, [_vp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _ip, _ip]),
     ("mpcq_replace_trajectories", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _dp, _ip]),
     ("mpcq_get_trajectories", ctypes.c_int, [_vp, _dp, _ip]),
     ("mpcq_mission_set", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
                                         ctypes.c_int32, _np, _ip]),
+    ("mpcq_mission_set_legs", ctypes.c_int, [_vp, _legp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _np,
+                                             _ip]),
     ("mpcq_mission_get", ctypes.c_int, [_vp, _ip, _ip, _ip, _ip, _ip, _dp]),
     ("mpcq_mission_stop", ctypes.c_int, [_vp]),
     ("mpcq_record_start", ctypes.c_int, [_vp, _ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

@@ -22,6 +22,7 @@
 #include "../../include/mpcq.h"
 #include "mpcq_kernels.hpp"
 #include "mpcq_replan.hpp"
+#include "mpcq_circle.hpp"
 #include "mpcq_replan_nl.hpp"
 #include "mpcq_mission.hpp"
 #include "mpcq_record.hpp"
@@ -217,10 +218,11 @@ struct Recorder {
 struct Mission {
   bool on = false;
   int L = 0, n_wp = 0, order = 0, nonlinear = 0;
-  double v_max = 0, a_max = 0, dt = 0;
+  double dt = 0;
   mpcq_nl::Opts opts;
   long long periods = 0;   // periods issued since mpcq_mission_set
-  DevBuf<double> d_wp;     // [B,L,n_wp,3]
+  DevBuf<double> d_wp;     // [B,L,n_wp,3] (empty: no waypoint leg)
+  DevBuf<mpcq_leg> d_legs; // [B,L]: kind, limits and radius of every leg
   DevBuf<double> d_info;   // [B,6] (nonlinear)
   DevBuf<int> d_int;       // leg [B] | installed [B] | last_code [B] | claim [B] | leg_code [B,L] | leg_period [B,L]
 };
@@ -387,9 +389,9 @@ void mission_launch(mpcq_engine* e, hipStream_t s, int b0, int n, const double* 
   const size_t B = e->B;
   rp::MissionArgs a;
   a.traj = t.traj; a.Tmax = t.Tmax; a.lens = t.len; a.idx = t.idx; a.finished = t.finished;
-  a.start = start; a.wp = ms.d_wp.p;
+  a.start = start; a.wp = ms.d_wp.p; a.legs = ms.d_legs.p;
   a.L = ms.L; a.n_wp = ms.n_wp; a.order = ms.order;
-  a.v_max = ms.v_max; a.a_max = ms.a_max; a.dt = ms.dt;
+  a.dt = ms.dt;
   a.b0 = b0; a.n = n; a.period = period;
   int* d = ms.d_int.p;
   a.leg = d; a.installed = d + B; a.last_code = d + 2 * B; a.claim = d + 3 * B;
@@ -1127,9 +1129,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.5 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.6 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.5 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.6 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1406,6 +1408,37 @@ int mpcq_replan_nonlinear(mpcq_engine* e, const double* start, const double* wp,
   return 0;
 }
 
+// The reference's 'circle' request (mpcq_circle.hpp): closed-form circle flights generated on the device.
+int mpcq_replan_circle(mpcq_engine* e, const double* start, const double* radius, const double* v_max, int32_t kind, double dt, double t_max,
+                       const int32_t* mask, int32_t* out) {
+  ENTER(e);
+  const std::string who("mpcq_replan_circle");
+  if (!radius || !v_max) return fail(MPCQ_ERR_INVALID, who + ": null radius or v_max");
+  if (kind != MPCQ_CIRCLE_ACC_DEC && kind != MPCQ_CIRCLE_CONSTANT && kind != MPCQ_CIRCLE_ACCELERATING) return fail(MPCQ_ERR_INVALID, who + ": unknown kind");
+  if (!(dt > 0 && std::isfinite(dt))) return fail(MPCQ_ERR_INVALID, who + ": dt must be finite and > 0");
+  if (kind == MPCQ_CIRCLE_ACCELERATING && !(t_max > 0 && std::isfinite(t_max))) return fail(MPCQ_ERR_INVALID, who + ": t_max must be finite and > 0");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, who + " without start points needs mpcq_sim_reset first (the plant state)");
+  const size_t B = e->B;
+  HIP_TRY(e->d_rp_in.grow(B * 5));   // radius [B] | v_max [B] | starts [B,3]
+  HIP_TRY(e->d_rp_int.grow(3 * B));
+  double* d_in = e->d_rp_in.p;
+  int* d_int = e->d_rp_int.p;
+  HIP_TRY(hipMemcpyAsync(d_in, radius, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(d_in + B, v_max, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (start) HIP_TRY(hipMemcpyAsync(d_in + 2 * B, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(d_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  int* d_code = d_int + B;
+  hipLaunchKernelGGL(mpcq::replan::circle_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
+                     start ? (const double*)(d_in + 2 * B) : t.plant, start ? 3 : 13, (const double*)d_in, (const double*)(d_in + B), (int)kind, dt, t_max,
+                     mask ? (const int*)d_int : (const int*)nullptr, d_code);
+  HIP_TRY(hipGetLastError());
+  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count, const double* traj, const int32_t* len) {
   ENTER(e);
   if (!idx || !traj || !len) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: null argument");
@@ -1435,6 +1468,43 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
 }
 
 // ---- device missions (mpcq_mission.hpp; the launch: mission_launch, behind every period of EngineT::period)
+namespace {
+// What mpcq_mission_set and mpcq_mission_set_legs (`who`) end in, behind their argument checks: the queue, the legs table, the leg counters
+// and an empty log on the device, the mission on.  wp may be NULL (no waypoint leg; n_wp is 0 then).
+int mission_begin(const std::string& who, mpcq_engine* e, const mpcq_leg* legs, const double* wp, int32_t L, int32_t n_wp, int32_t order, double dt,
+                  int32_t nonlinear, const mpcq_nl::Opts& o, const int32_t* leg0) {
+  const size_t B = e->B, nl = B * (size_t)L;
+  if (nl * (n_wp > 0 ? n_wp : 1) * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  if (leg0)
+    for (size_t b = 0; b < B; ++b)
+      if (leg0[b] < 0 || leg0[b] > L) return fail(MPCQ_ERR_INVALID, who + ": leg0 outside 0..L");
+  const TrajSlots t = e->traj_slots();
+  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still read the queue that is replaced)
+  Mission& ms = e->ms;
+  ms.on = false;
+  if (wp) HIP_TRY(ms.d_wp.grow(nl * n_wp * 3));
+  else ms.d_wp.release();
+  HIP_TRY(ms.d_legs.grow(nl));
+  HIP_TRY(ms.d_int.grow(4 * B + 2 * nl));
+  if (nonlinear) HIP_TRY(ms.d_info.grow(B * 6));
+  std::vector<int> h(4 * B + 2 * nl, 0);   // leg | installed | last_code | claim | leg_code | leg_period
+  for (size_t b = 0; b < B; ++b) { h[b] = leg0 ? leg0[b] : 0; h[2 * B + b] = MPCQ_REPLAN_SKIPPED; }
+  for (size_t k = 0; k < nl; ++k) { h[4 * B + k] = MPCQ_REPLAN_SKIPPED; h[4 * B + nl + k] = -1; }
+  if (wp) HIP_TRY(hipMemcpyAsync(ms.d_wp.p, wp, nl * n_wp * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(ms.d_legs.p, legs, nl * sizeof(mpcq_leg), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(ms.d_int.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  const std::vector<double> nan(nonlinear ? B * 6 : 0, std::nan(""));   // (info: NaN rows until a flight is installed)
+  if (nonlinear) HIP_TRY(hipMemcpyAsync(ms.d_info.p, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  ms.L = L; ms.n_wp = wp ? n_wp : 0; ms.order = order; ms.nonlinear = nonlinear;
+  ms.dt = dt; ms.opts = o;
+  ms.periods = 0;
+  ms.on = true;
+  return 0;
+}
+}  // namespace
+
 int mpcq_mission_set(mpcq_engine* e, const double* wp, int32_t L, int32_t n_wp, double v_max, double a_max, int32_t derivative_to_optimize, double dt,
                      int32_t nonlinear, const mpcq_minsnap_nl_options* opts, const int32_t* leg0) {
   ENTER(e);
@@ -1449,32 +1519,36 @@ int mpcq_mission_set(mpcq_engine* e, const double* wp, int32_t L, int32_t n_wp, 
   if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
   const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
   if (nonlinear && !mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
-  const size_t B = e->B, nl = B * (size_t)L;
-  if (nl * n_wp * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
-  if (leg0)
-    for (size_t b = 0; b < B; ++b)
-      if (leg0[b] < 0 || leg0[b] > L) return fail(MPCQ_ERR_INVALID, who + ": leg0 outside 0..L");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still read the queue that is replaced)
-  Mission& ms = e->ms;
-  ms.on = false;
-  HIP_TRY(ms.d_wp.grow(nl * n_wp * 3));
-  HIP_TRY(ms.d_int.grow(4 * B + 2 * nl));
-  if (nonlinear) HIP_TRY(ms.d_info.grow(B * 6));
-  std::vector<int> h(4 * B + 2 * nl, 0);   // leg | installed | last_code | claim | leg_code | leg_period
-  for (size_t b = 0; b < B; ++b) { h[b] = leg0 ? leg0[b] : 0; h[2 * B + b] = MPCQ_REPLAN_SKIPPED; }
-  for (size_t k = 0; k < nl; ++k) { h[4 * B + k] = MPCQ_REPLAN_SKIPPED; h[4 * B + nl + k] = -1; }
-  HIP_TRY(hipMemcpyAsync(ms.d_wp.p, wp, nl * n_wp * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(ms.d_int.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  const std::vector<double> nan(nonlinear ? B * 6 : 0, std::nan(""));   // (info: NaN rows until a flight is installed)
-  if (nonlinear) HIP_TRY(hipMemcpyAsync(ms.d_info.p, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  ms.L = L; ms.n_wp = n_wp; ms.order = derivative_to_optimize; ms.nonlinear = nonlinear;
-  ms.v_max = v_max; ms.a_max = a_max; ms.dt = dt; ms.opts = o;
-  ms.periods = 0;
-  ms.on = true;
-  return 0;
+  if ((size_t)e->B * (size_t)L > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  // the special case of mpcq_mission_set_legs: every leg a waypoint leg with the call's limits
+  mpcq_leg one;
+  one.kind = MPCQ_LEG_WAYPOINTS; one.reserved = 0; one.v_max = v_max; one.a_max = a_max; one.radius = 0.0;
+  const std::vector<mpcq_leg> legs((size_t)e->B * (size_t)L, one);
+  return mission_begin(who, e, legs.data(), wp, L, n_wp, derivative_to_optimize, dt, nonlinear, o, leg0);
+}
+int mpcq_mission_set_legs(mpcq_engine* e, const mpcq_leg* legs, const double* wp, int32_t L, int32_t n_wp, int32_t derivative_to_optimize, double dt,
+                          int32_t nonlinear, const mpcq_minsnap_nl_options* opts, const int32_t* leg0) {
+  ENTER(e);
+  const std::string who("mpcq_mission_set_legs");
+  if (!legs) return fail(MPCQ_ERR_INVALID, who + ": null legs");
+  if (L < 1) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
+  if (wp && (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1)) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
+  if (nonlinear != 0 && nonlinear != 1) return fail(MPCQ_ERR_INVALID, who + ": nonlinear must be 0 or 1");
+  if (!(dt > 0 && std::isfinite(dt))) return fail(MPCQ_ERR_INVALID, who + ": dt must be finite and > 0");
+  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
+  const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
+  if (nonlinear && !mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
+  if ((size_t)e->B * (size_t)L > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  auto positive = [](double x) { return x > 0 && std::isfinite(x); };
+  for (size_t k = 0, nl = (size_t)e->B * (size_t)L; k < nl; ++k) {
+    const mpcq_leg& lg = legs[k];
+    if (lg.kind != MPCQ_LEG_WAYPOINTS && lg.kind != MPCQ_LEG_CIRCLE) return fail(MPCQ_ERR_INVALID, who + ": unknown leg kind");
+    if (lg.reserved != 0) return fail(MPCQ_ERR_INVALID, who + ": reserved must be 0");
+    if (lg.kind == MPCQ_LEG_WAYPOINTS && !wp) return fail(MPCQ_ERR_INVALID, who + ": a waypoint leg needs waypoints");
+    if (!positive(lg.v_max) || !positive(lg.a_max) || (lg.kind == MPCQ_LEG_CIRCLE && !positive(lg.radius)))
+      return fail(MPCQ_ERR_INVALID, who + ": v_max, a_max and (circle legs) radius of every leg must be finite and > 0");
+  }
+  return mission_begin(who, e, legs, wp, L, wp ? n_wp : 0, derivative_to_optimize, dt, nonlinear, o, leg0);   // (n_wp is not read without wp)
 }
 int mpcq_mission_get(mpcq_engine* e, int32_t* leg, int32_t* installed, int32_t* last_code, int32_t* leg_code, int32_t* leg_period, double* info) {
   ENTER(e);

@@ -1,8 +1,12 @@
 // mpcq_mission.hpp — device missions (mpcq_mission_set): a queue of upcoming flights per quadrotor and one launch behind every period that
-// installs the next flight for whoever just finished, with no host in between.  Included from mpcq_api.hip after mpcq_replan_nl.hpp.
+// installs the next flight for whoever just finished, with no host in between.  Included from mpcq_api.hip after mpcq_replan_nl.hpp and
+// mpcq_circle.hpp.
 //
-// The flight itself is mpcq_replan's (plan_linear) or mpcq_replan_nonlinear's (plan_nonlinear): the same device function the host calls
-// run, so a mission plans bit for bit what the host loop `sim_steps(1); replan(wp[b, leg[b]], mask = finished & (leg < L))` plans.
+// The flight itself is mpcq_replan's (plan_linear), mpcq_replan_nonlinear's (plan_nonlinear) or mpcq_replan_circle's (plan_circle), as the
+// leg's entry of the legs table says and with that entry's limits: the same device function the host calls run, so a mission plans bit
+// for bit what the host loop plans that runs, behind every `sim_steps(1)`, over the quadrotors due (finished & (leg < L)):
+// `replan_circle(radius, v_max, mask = circle legs due)`, then `replan(wp[b, leg[b]], v, a, mask = waypoint legs due with these limits)`
+// once per distinct pair of limits (v, a) among them, then `leg += 1`.  (mpcq_mission_set: no circle leg and one pair of limits, so one replan.)
 //  * The grid does not depend on how many quadrotors finished: workgroups of one wavefront, about one per 16 quadrotors of the range.
 //  * Every workgroup sweeps the flags of the whole range once, 64 per load, from a start point of its own (its share comes first), and plans
 //    the candidates it wins one after another.  A candidate is won by a compare-and-swap on its ticket claim[b] (old value -> this period's
@@ -19,9 +23,10 @@ namespace replan {
 struct MissionArgs {
   double* traj; int Tmax; int *lens, *idx, *finished;   // the trajectory slots (TrajSlots)
   const double* start;        // [B,13]: the plant state behind the period's update, or the period's measurement
-  const double* wp;           // [B,L,n_wp,3]
+  const double* wp;           // [B,L,n_wp,3] (not read for a circle leg; nullptr if the queue has no waypoint leg)
+  const mpcq_leg* legs;       // [B,L]: kind, limits and radius of every leg (mpcq_mission_set: the same waypoint leg everywhere)
   int L, n_wp, order;
-  double v_max, a_max, dt;
+  double dt;
   int b0, n;                  // the range [b0, b0 + n) of this launch (a group of mpcq_sim_steps, or the batch)
   int period;                 // period number since mpcq_mission_set
   int *leg, *installed, *last_code, *claim;   // [B]
@@ -41,13 +46,17 @@ inline int mission_grid(int n) {
   return g < 1 ? 1 : (g > MISSION_MAX_GRID ? MISSION_MAX_GRID : g);
 }
 
-__device__ inline int mission_plan(MissionLds<Lds>& M, const MissionArgs& a, const mpcq_nl::Opts&, int b, const double* wp_b) {
-  return plan_linear(M.plan, a.traj, a.Tmax, a.lens, a.idx, a.finished, b, a.start + (size_t)b * NX, wp_b, a.n_wp, a.v_max, a.a_max, a.order, a.dt);
+// a waypoint leg with the limits of its table entry
+__device__ inline int mission_plan(MissionLds<Lds>& M, const MissionArgs& a, const mpcq_nl::Opts&, int b, const double* wp_b, double v_max, double a_max) {
+  return plan_linear(M.plan, a.traj, a.Tmax, a.lens, a.idx, a.finished, b, a.start + (size_t)b * NX, wp_b, a.n_wp, v_max, a_max, a.order, a.dt);
 }
-__device__ inline int mission_plan(MissionLds<NlLds>& M, const MissionArgs& a, const mpcq_nl::Opts& o, int b, const double* wp_b) {
-  return plan_nonlinear(M.plan, a.traj, a.Tmax, a.lens, a.idx, a.finished, b, a.start + (size_t)b * NX, wp_b, a.n_wp, a.v_max, a.a_max, a.order, a.dt, o,
+__device__ inline int mission_plan(MissionLds<NlLds>& M, const MissionArgs& a, const mpcq_nl::Opts& o, int b, const double* wp_b, double v_max, double a_max) {
+  return plan_nonlinear(M.plan, a.traj, a.Tmax, a.lens, a.idx, a.finished, b, a.start + (size_t)b * NX, wp_b, a.n_wp, v_max, a_max, a.order, a.dt, o,
                         M.info, nullptr, nullptr);
 }
+// the LDS a circle leg works in: the linear generator's
+__device__ inline Lds& mission_circle_lds(Lds& S) { return S; }
+__device__ inline Lds& mission_circle_lds(NlLds& L) { return L.base; }
 
 template <typename LdsT>
 __global__ __launch_bounds__(64) void mission_kernel(const MissionArgs a, const mpcq_nl::Opts o) {
@@ -77,7 +86,11 @@ __global__ __launch_bounds__(64) void mission_kernel(const MissionArgs a, const 
       __syncthreads();
       const int leg = M.leg;
       if (!M.won || leg >= a.L) continue;
-      const int code = mission_plan(M, a, o, bn, a.wp + ((size_t)bn * a.L + leg) * a.n_wp * 3);
+      const mpcq_leg lg = a.legs[(size_t)bn * a.L + leg];   // (every lane loads the same entry)
+      const bool circle = lg.kind == MPCQ_LEG_CIRCLE;
+      const int code = circle ? plan_circle(mission_circle_lds(M.plan), a.traj, a.Tmax, a.lens, a.idx, a.finished, bn, a.start + (size_t)bn * NX, lg.radius,
+                                            lg.v_max, CIRCLE_ACC_DEC, a.dt, 0.0)
+                              : mission_plan(M, a, o, bn, a.wp + ((size_t)bn * a.L + leg) * a.n_wp * 3, lg.v_max, lg.a_max);
       __syncthreads();
       // the leg is consumed whatever the code (a negative one left trajectory, cursor and flag as they were: the next period tries the next leg)
       if (lane == 0) {
@@ -87,7 +100,7 @@ __global__ __launch_bounds__(64) void mission_kernel(const MissionArgs a, const 
         a.leg_period[(size_t)bn * a.L + leg] = a.period;
         if (code == DONE) a.installed[bn] = a.installed[bn] + 1;
       }
-      if (a.info && code == DONE && lane < 6) a.info[(size_t)bn * 6 + lane] = M.info[lane];
+      if (a.info && code == DONE && lane < 6) a.info[(size_t)bn * 6 + lane] = circle ? __builtin_nan("") : M.info[lane];   // (a circle has no info row)
     }
   }
 }

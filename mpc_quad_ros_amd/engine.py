@@ -44,6 +44,10 @@ WARM_BUDGET, WARM_PINS, WARM_WRONG, WARM_BOUNCE, WARM_NUMERIC, WARM_SKIPPED = 1,
 SOLVE_LOW_ACCURACY = 8
 # per-quadrotor result codes of Engine.replan (include/mpcq.h MPCQ_REPLAN_*)
 REPLAN_DONE, REPLAN_SKIPPED, REPLAN_BAD_INPUT, REPLAN_SINGULAR, REPLAN_LIMITS, REPLAN_TOO_LONG = 0, 1, -1, -2, -3, -4
+# circle flights of Engine.replan_circle (include/mpcq.h MPCQ_CIRCLE_*) and leg kinds of Engine.mission_set_legs (MPCQ_LEG_*)
+CIRCLE_KINDS = {"acc_dec": 0, "constant": 1, "accelerating": 2}
+LEG_WAYPOINTS, LEG_CIRCLE = 0, 1
+LEG_DTYPE = np.dtype([("kind", np.int32), ("reserved", np.int32), ("v_max", np.float64), ("a_max", np.float64), ("radius", np.float64)])
 
 
 # flight recorder fields (include/mpcq.h MPCQ_RECORD_*): name -> bit
@@ -134,6 +138,22 @@ class Engine:
                                                    None if o is None else ctypes.byref(o), _lib.d(info), _lib.d(pieces), _lib.d(d_free)))
         return (out, info, pieces, d_free) if return_pieces else (out, info)
 
+    def replan_circle(self, radius, v_max, kind="acc_dec", dt=0.01, t_max=10.0, start=None, mask=None):
+        """Circle flights generated on the device (mpcq_replan_circle) -- what trajectories.circle_trajectory(kind, radius[b], v_max[b], dt,
+        t_max, start_b) makes on the host -- for the selected quadrotors, installed as replan installs.  radius, v_max: scalars or [B];
+        kind: 'acc_dec' (the reference node's circle request), 'constant' or 'accelerating' (the only one that reads t_max); start
+        [B,3] (None: the on-device plant's position).  Returns the per-quadrotor codes [B] (REPLAN_*)."""
+        if kind not in CIRCLE_KINDS:
+            raise ValueError(f"kind must be one of {sorted(CIRCLE_KINDS)}")
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (self.B,)))
+        v_max = np.ascontiguousarray(np.broadcast_to(np.asarray(v_max, dtype=np.float64), (self.B,)))
+        start = self._f(start, (self.B, 3))
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.B)
+        out = np.zeros(self.B, np.int32)
+        self._check(self.lib.mpcq_replan_circle(self.h, _lib.d(start), _lib.d(radius), _lib.d(v_max), CIRCLE_KINDS[kind], float(dt), float(t_max),
+                                                _lib.i(mask), _lib.i(out)))
+        return out
+
     def replace_trajectories(self, idx, traj, lengths):
         """Host-made rows traj [count, Tmax, 13] (the first lengths[j] used) into the slots of quadrotors idx [count]."""
         idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
@@ -167,6 +187,36 @@ class Engine:
         self._check(self.lib.mpcq_mission_set(self.h, _lib.d(wp), wp.shape[1], wp.shape[2], float(v_max), float(a_max), int(order), float(dt),
                                               int(bool(nonlinear)), None if o is None else ctypes.byref(o), _lib.i(leg0)))
         self._mission_legs = wp.shape[1]
+
+    def mission_set_legs(self, legs, wp=None, order=4, dt=0.01, nonlinear=False, opts=None, leg0=None):
+        """mission_set with a kind and limits per leg (mpcq_mission_set_legs).  legs: a structured array [B, L] of LEG_DTYPE, or a dict
+        of [B, L] arrays (or scalars) `kind` (LEG_WAYPOINTS / LEG_CIRCLE, or 'waypoints' / 'circle'), `v_max`, `a_max` and -- for circle
+        legs -- `radius` (trajectories.mission_legs builds one).  A waypoint leg is replan's flight through wp[b, leg] with the leg's
+        limits, a circle leg replan_circle's 'acc_dec' circle of the leg's radius and v_max from where the quadrotor stands.
+        wp [B, L, n_wp, 3]; None if every leg is a circle."""
+        if isinstance(legs, dict):
+            unknown = set(legs) - {"kind", "v_max", "a_max", "radius"}
+            if unknown or not {"kind", "v_max", "a_max"} <= set(legs):
+                raise ValueError("legs needs kind, v_max, a_max and (circle legs) radius")
+            shape = np.broadcast_shapes(*(np.shape(v) for v in legs.values()))
+            if len(shape) != 2 or shape[0] != self.B:
+                raise ValueError(f"the arrays of legs must be [B={self.B}, L]")
+            from .trajectories import mission_legs
+            legs = mission_legs(self.B, shape[1], legs["v_max"], legs["a_max"], legs["kind"], legs.get("radius", 0.0))
+        legs = np.ascontiguousarray(legs)
+        if legs.dtype != LEG_DTYPE or legs.ndim != 2 or legs.shape[0] != self.B:
+            raise ValueError(f"legs must be a [B={self.B}, L] array of engine.LEG_DTYPE")
+        L, n_wp = legs.shape[1], 0
+        if wp is not None:
+            wp = self._f(wp)
+            if wp.ndim != 4 or wp.shape[0] != self.B or wp.shape[1] != L or wp.shape[3] != 3:
+                raise ValueError(f"wp must be [B={self.B}, L={L}, n_wp, 3]")
+            n_wp = wp.shape[2]
+        leg0 = None if leg0 is None else np.ascontiguousarray(leg0, dtype=np.int32).reshape(self.B)
+        o = _lib.nl_options(opts) if nonlinear else None
+        self._check(self.lib.mpcq_mission_set_legs(self.h, legs.ctypes.data_as(ctypes.POINTER(_lib.Leg)), _lib.d(wp), L, n_wp, int(order), float(dt),
+                                                   int(bool(nonlinear)), None if o is None else ctypes.byref(o), _lib.i(leg0)))
+        self._mission_legs = L
 
     def mission_get(self):
         """The mission's state: leg [B] (legs consumed), installed [B] (flights installed), last_code [B], leg_code [B, L] (REPLAN_*;

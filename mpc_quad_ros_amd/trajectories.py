@@ -298,6 +298,24 @@ def mission_waypoints(seed: int, first_index: int, count: int, legs: int, num_wa
                     ).reshape(count, legs, num_waypoints, 3)
 
 
+def mission_legs(count: int, legs: int, v_max, a_max=None, kind="waypoints", radius=10.0):
+    """The legs table of a speed sweep (Engine.mission_set_legs), a structured array [count, legs] of engine.LEG_DTYPE: quadrotor i flies
+    leg l at v_max[i, l].  v_max, a_max (None: = v_max, as the reference's sweeps v3_a3 .. v12_a12), kind ('waypoints' / 'circle' or
+    the LEG_* values) and radius (read for circle legs) are scalars or anything that broadcasts to [count, legs]: a [count, 1] column is
+    a sweep over the swarm, a [legs] row raises the speed from flight to flight as the reference's Explorer does."""
+    from .engine import LEG_CIRCLE, LEG_DTYPE, LEG_WAYPOINTS
+    table = np.zeros((count, legs), LEG_DTYPE)
+    kind = np.asarray(kind)
+    if kind.dtype.kind in "US":
+        names = {"waypoints": LEG_WAYPOINTS, "circle": LEG_CIRCLE}
+        kind = np.vectorize(names.__getitem__, otypes=[np.int32])(kind)
+    table["kind"] = kind
+    table["v_max"] = v_max
+    table["a_max"] = v_max if a_max is None else a_max
+    table["radius"] = np.where(table["kind"] == LEG_CIRCLE, radius, 0.0)
+    return table
+
+
 def _mission_chunk(args):
     """Worker: missions of a contiguous index block, as float32-free compact rows (positions and velocities; the other
     columns of a reference are constants)."""
