@@ -149,8 +149,8 @@ const char* mpcq_last_error(void);
  * recipe the library was built from (csrc/Makefile SRC_ID = bench.kernel_source_sha16()); profiles under profiles/ carry the same hash.
  * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
  * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp), since 0.6.3 the flight recorder (csrc/mpcq_record.hpp), since 0.6.4 the RGP
- * read-out (csrc/mpcq_predict.hpp), since 0.6.5 the device missions (csrc/mpcq_mission.hpp) and, since 0.6.6, the device circle generator
- * (csrc/mpcq_circle.hpp). */
+ * read-out (csrc/mpcq_predict.hpp), since 0.6.5 the device missions (csrc/mpcq_mission.hpp), since 0.6.6 the device circle generator
+ * (csrc/mpcq_circle.hpp) and, since 0.6.7, the flight scoreboard (csrc/mpcq_score.hpp). */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -462,6 +462,62 @@ int mpcq_record_get_periods(mpcq_engine* e, int64_t* out /*[rows]: the period nu
 int mpcq_record_clear(mpcq_engine* e);
 /* frees the buffers; recording off.  get / info / clear / stop without an active recording: MPCQ_ERR_STATE. */
 int mpcq_record_stop(mpcq_engine* e);
+
+/* ---- flight scoreboard (since 0.6.7): the reference evaluates a run flight by flight -- src/compare_trajectories.py:40-51 plots, per
+ * flight, max ||v|| against the mean of the per-step rms_pos of src/Visualiser.py:805-822 and leaves out the last second "because it
+ * tries to stop in place".  Here a table score [B, F, 16] of doubles lives on the device and one small launch behind every period folds
+ * that period into the row of the flight the quadrotor is flying; the host reads the table once, at the end of a sweep.  A period is
+ * what the flight recorder and the missions count: one mpcq_step / mpcq_step_device_async call, one iteration of mpcq_sim_steps /
+ * mpcq_sim_control_periods; mpcq_solve is not a period.  On the stream of a period the order is: recorder snapshot -> ordering launch ->
+ * step -> recorder row -> score -> plant -> mission, so the score reads what a recorded row shows: the measurement x the step solved
+ * from, the cursor i the step used, ref = row 0 of the reference chunk the step used (MPCQ_RECORD_X_REF), status, qp_iter, cost and the
+ * finished flag after the step.  Scoring changes no result of the engine, and with no score running every launch sequence is what it was.
+ *
+ * One period of quadrotor b, with cur[b] its current slot (0 at the start) and len the length of its trajectory:
+ *  1. A flight begins with a period whose step used cursor 0: if i == 0 and slot cur[b] already holds a period, cur[b] += 1.  No install
+ *     path is hooked: a mission's install, mpcq_replan*, mpcq_replace_trajectories and mpcq_set_trajectories all open a slot this way
+ *     (and so does mpcq_reset or mpcq_set_state(idx = 0): they are allowed while a score is running and show as a new flight, as they
+ *     show in later rows of a recording).  A score started in mid-flight puts the partial flight into slot 0.
+ *  2. If cur[b] >= F: overflow[b] += 1 and nothing else is written for this period (cur[b] stays at F).
+ *  3. The period is a tail period iff i >= len - tail_rows.  tail_rows = 0: exactly the periods beyond the flight's last row (a quadrotor
+ *     that holds its last reference row, or overshot without finishing); tail_rows = 100: the reference's dropped last second at 100 Hz rows.
+ *  4. With ep = sum_k (x[k] - ref[k])^2, ev = sum_k (x[7+k] - ref[7+k])^2, v2 = sum_k x[7+k]^2, vr2 = sum_k ref[7+k]^2 over k = 0..2 the
+ *     row of slot cur[b] is updated.  Every field starts at 0, except 12 and 13, which start at -1; counts are doubles and stay exact:
+ *       #  name             updated in     value
+ *       0  steps            non-tail       += 1
+ *       1  sum_epos2        non-tail       += ep
+ *       2  sum_evel2        non-tail       += ev
+ *       3  max_epos2        non-tail       max(., ep)
+ *       4  sum_rms_pos      non-tail       += sqrt(ep / 3)   (Visualiser's per-step rms_pos)
+ *       5  max_v2           non-tail       max(., v2)
+ *       6  max_vref2        non-tail       max(., vr2)
+ *       7  sum_cost         non-tail       += cost[b]
+ *       8  tail_steps       tail           += 1
+ *       9  bad_status       every period   += (status != 0)
+ *      10  fallbacks        every period   += (qp_iter / 1000 % 10 != 0)
+ *      11  factorisations   every period   += qp_iter % 1000
+ *      12  first_period     every period   set once: the period number (since mpcq_score_start / mpcq_score_clear) of the slot's first period
+ *      13  last_period      every period   = the period number
+ *      14  rows             every period   = len
+ *      15  finished         every period   = 1 once the finished flag is set after a step of this flight
+ * Quadrotors are independent and updated in period order on the stream of their group: the table does not depend on mpcq_tuning.groups.
+ * A running score is not part of a checkpoint, and nothing is reduced across ranks (a score is per shard, as a recording is). */
+#define MPCQ_SCORE_WIDTH 16
+/* Starts a score with `flights` = F >= 1 slots per quadrotor (memory: B x F x 128 bytes) from the next period on; while one is running it
+ * is replaced (table, slots and period count start again).  MPCQ_ERR_INVALID: flights < 1, tail_rows < 0, and a table of B x F x 16 >= 2^31
+ * doubles (16 GiB: refused before anything is allocated, so that the element counts of the launches and of the copy stay within 32 bits).
+ * MPCQ_ERR_STATE: before mpcq_set_trajectories.  mpcq_sim_run (one persistent launch) scores nothing: MPCQ_ERR_STATE while a score is
+ * running. */
+int mpcq_score_start(mpcq_engine* e, int32_t flights /*F >= 1 slots per quadrotor*/, int32_t tail_rows /*>= 0*/);
+/* The table, behind everything the engine has enqueued on every group stream; every pointer may be NULL.  flights [B]: slots that hold
+ * a period (0..F); overflow [B]: periods that found no slot; periods: periods counted since mpcq_score_start / mpcq_score_clear (per
+ * quadrotor the sum over its slots of steps + tail_steps, plus overflow[b], equals it).  MPCQ_ERR_STATE: no score running. */
+int mpcq_score_get(mpcq_engine* e, double* score /*[B,F,16] or NULL*/, int32_t* flights /*[B] or NULL: slots holding a period*/,
+                   int32_t* overflow /*[B] or NULL*/, int64_t* periods /*or NULL: periods since score_start / score_clear*/);
+/* table, cur, overflow and period count back to the start values; stays on.  MPCQ_ERR_STATE: no score running. */
+int mpcq_score_clear(mpcq_engine* e);
+/* off, buffers freed: period launches are exactly what they are without it.  MPCQ_ERR_STATE: no score running. */
+int mpcq_score_stop(mpcq_engine* e);
 
 /* ---- RGP read-out with uncertainty (since 0.6.4): GPEnsemble.predict(X_t, std=True) (src/gp/GPE.py:165-201) over RGP.predict
  * (src/gp/RGP.py:168-229) for every quadrotor and axis, evaluated on the device.  With the axis' basis X, theta = (L, sigma_f, sigma_n),

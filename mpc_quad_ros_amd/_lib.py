@@ -121,6 +121,10 @@ SYMBOLS = [
     ("mpcq_record_get_periods", ctypes.c_int, [_vp, _lp]),
     ("mpcq_record_clear", ctypes.c_int, [_vp]),
     ("mpcq_record_stop", ctypes.c_int, [_vp]),
+    ("mpcq_score_start", ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    ("mpcq_score_get", ctypes.c_int, [_vp, _dp, _ip, _ip, _lp]),
+    ("mpcq_score_clear", ctypes.c_int, [_vp]),
+    ("mpcq_score_stop", ctypes.c_int, [_vp]),
     ("mpcq_rgp_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
     ("mpcq_record_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),

@@ -26,6 +26,7 @@
 #include "mpcq_replan_nl.hpp"
 #include "mpcq_mission.hpp"
 #include "mpcq_record.hpp"
+#include "mpcq_score.hpp"
 #include "mpcq_predict.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
@@ -226,6 +227,15 @@ struct Mission {
   DevBuf<double> d_info;   // [B,6] (nonlinear)
   DevBuf<int> d_int;       // leg [B] | installed [B] | last_code [B] | claim [B] | leg_code [B,L] | leg_period [B,L]
 };
+// The flight scoreboard (mpcq_score_*, mpcq_score.hpp): one row of 16 doubles per quadrotor and flight slot on the device, folded by a launch
+// behind every period (EngineT::score_write).
+struct Score {
+  bool on = false;
+  int F = 0, tail_rows = 0;
+  long long periods = 0;    // periods issued since mpcq_score_start / mpcq_score_clear
+  DevBuf<double> d_table;   // [B,F,16]
+  DevBuf<int> d_int;        // cur [B] | used [B] | overflow [B]
+};
 // Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
 // on a stream of its own, the event that marks the end of its part of a call.
 struct Group {
@@ -277,6 +287,8 @@ struct mpcq_engine : EngineQueues {
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
   Mission ms;                    // mpcq_mission_set .. mpcq_mission_stop
   int mission_next_period() { return ms.on ? (int)ms.periods++ : -1; }   // the number of the period about to be issued (-1: no mission)
+  Score sc;                      // mpcq_score_start .. mpcq_score_stop
+  long long score_next_period() { return sc.on ? sc.periods++ : -1; }     // the same for the scoreboard (-1: no score running)
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
   std::vector<double> kxinv64;
   struct PredictScratch {
@@ -800,6 +812,16 @@ struct EngineT : mpcq_engine {
     a.Tmax = m.Tmax; a.N = N; a.skip = m.skip; a.nb = nb; a.dt_pred = m.dt_pred;
     hipLaunchKernelGGL(mpcq::record::record_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
   }
+  // behind the recorder's row, in front of any plant launch: period `sper` of the scoreboard for the quadrotors [b0, b0 + n)
+  void score_write(hipStream_t s, int b0, int n, long long sper, const double* xmeas) {
+    mpcq::score::Args a;
+    a.table = sc.d_table.p; a.cur = sc.d_int.p; a.used = a.cur + B; a.overflow = a.cur + 2 * (size_t)B;
+    a.F = sc.F; a.tail_rows = sc.tail_rows; a.b0 = b0; a.n = n; a.period = (double)sper;
+    a.xmeas = xmeas; a.cost = st.cost; a.traj = st.traj;
+    a.tlen = st.tlen; a.idx = st.idx; a.finished = st.finished; a.status = st.status; a.qp_iter = st.qp_iter;
+    a.Tmax = m.Tmax; a.N = N; a.skip = m.skip;
+    hipLaunchKernelGGL(mpcq::score::score_kernel, dim3(mpcq::score::grid((long)n * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, a);
+  }
   // one lockstep period of the quadrotors [b0, b0 + nq) on stream `strm`; ev_begin (if any) is recorded in front of the STEP kernel, behind
   // the ordering launch, so that the event pairs of sim_steps time the step kernel alone
   void launch_period(const mpcq::DevState<T>& s, int mode, hipEvent_t ev_begin, hipStream_t strm, int b0, int nq) {
@@ -813,11 +835,12 @@ struct EngineT : mpcq_engine {
     hipLaunchKernelGGL(kstep, dim3(nq), dim3(64), lds_bytes, strm, m, so, mode);
   }
   // One period of groups[gi], the only place that issues one.  On the group's stream, in this order: the recorder's snapshot (row >= 0:
-  // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the plant kernel
+  // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the scoreboard's launch
+  // (sper >= 0: a score is running and this is its period number) -> the plant kernel
   // (plant: s.run_nsub substeps of s.run_dt on s.run_x) -> the mission launch (mper >= 0: a mission is active and this is its period
   // number; the flights start at the plant state behind its update, or without a plant at the period's measurement).  Every event is
   // optional.  The caller asks hipGetLastError once it has issued all it has to issue.
-  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
+  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, long long sper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
     const Group& g = groups[gi];
     if (g.n <= 0) return 0;
     if (row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
@@ -825,6 +848,7 @@ struct EngineT : mpcq_engine {
     launch_period(s, mode, ev_step, g.stream, g.b0, g.n);
     if (ev_end) HIP_TRY(hipEventRecord(ev_end, g.stream));
     if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
+    if (sper >= 0) score_write(g.stream, g.b0, g.n, sper, s.x_meas);
     if (plant)
       hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g.n + 63) / 64), dim3(64), 0, g.stream, m, s.run_x + (size_t)g.b0 * 13, st.w + (size_t)g.b0 * 4, s.run_nsub, s.run_dt, g.n);
     if (mper >= 0) mission_launch(this, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, mper);
@@ -834,7 +858,7 @@ struct EngineT : mpcq_engine {
     int rc;
     if ((rc = h2d(d_xin, x0, (size_t)B * 13))) return rc;
     st.x_meas = d_xin;
-    if ((rc = period(n_groups, st, 0, -1, -1, ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, 0, -1, -1, -1, ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -901,7 +925,7 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemcpyAsync(d_xin, h_pin, nx * sizeof(double), hipMemcpyHostToDevice, stream));
     st.x_meas = d_xin;
     int rc;
-    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), score_next_period(), ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipMemcpyAsync(h_pin + nx, st.w, nw * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -917,7 +941,7 @@ struct EngineT : mpcq_engine {
     s2.x_meas = d_x;
     s2.w_ext = d_w;   // the engine's own control record st.w is written as well (mpcq_get_command, mpcq_sim_plant_period(w = NULL))
     int rc;
-    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), score_next_period(), ev0, nullptr, ev1, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     return chk_after();   // (synchronises in the checked build only)
@@ -953,10 +977,11 @@ struct EngineT : mpcq_engine {
     for (int k = 0; k < K; ++k) {
       const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of a group cover the selection inside it)
       const int mper = mission_next_period();
+      const long long sper = score_next_period();
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
       for (int g = 0; g < G; ++g) {
         hipEvent_t* pair = g == 0 && k % stride == 0 ? &kev[2 * (k / stride)] : nullptr;
-        if ((rc = period(g, s2, mode, row, mper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
+        if ((rc = period(g, s2, mode, row, mper, sper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
       }
     }
     for (int g = 1; g < G; ++g) {
@@ -982,6 +1007,7 @@ struct EngineT : mpcq_engine {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_run needs mpcq_set_trajectories first");
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
+    if (sc.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot score flights (one persistent launch): mpcq_score_stop first, or use mpcq_sim_steps");
     if (K <= 0) return 0;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
@@ -1129,9 +1155,9 @@ const char* mpcq_last_error(void) { return g_err.c_str(); }
 #define MPCQ_SRC_ID "unknown"
 #endif
 #ifdef MPCQ_CHECKED
-const char* mpcq_version(void) { return "mpcq 0.6.6 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.7 (gfx950, CHECKED diagnostic build, source " MPCQ_SRC_ID ")"; }
 #else
-const char* mpcq_version(void) { return "mpcq 0.6.6 (gfx950, source " MPCQ_SRC_ID ")"; }
+const char* mpcq_version(void) { return "mpcq 0.6.7 (gfx950, source " MPCQ_SRC_ID ")"; }
 #endif
 
 // binaries built against the 0.3 header (source callers get the header's inline, which passes their own sizeof): the 0.3 layout ends
@@ -1690,6 +1716,68 @@ int mpcq_record_stop(mpcq_engine* e) {
   if (!e->rec.on) return fail(MPCQ_ERR_STATE, "mpcq_record_stop: no active recording");
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the buffers)
   e->rec = Recorder();
+  return 0;
+}
+
+// ---- flight scoreboard (mpcq_score.hpp; the launch: EngineT::score_write, behind the recorder's row of every period)
+namespace {
+// table, cur, used and overflow to their start values on the engine's stream, and the period count to 0
+int score_init(mpcq_engine* e) {
+  Score& sc = e->sc;
+  double* table = sc.d_table.p;
+  int* ints = sc.d_int.p;
+  const long B = e->B;
+  const int F = sc.F;
+  hipStream_t s = e->stream;
+  hipLaunchKernelGGL(mpcq::score::score_init_kernel, dim3(mpcq::score::grid(B * F * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, table, ints, B, F);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  sc.periods = 0;
+  return 0;
+}
+}  // namespace
+int mpcq_score_start(mpcq_engine* e, int32_t flights, int32_t tail_rows) {
+  ENTER(e);
+  if (flights < 1 || tail_rows < 0) return fail(MPCQ_ERR_INVALID, "mpcq_score_start: flights must be >= 1 and tail_rows >= 0");
+  if ((size_t)e->B * (size_t)flights * mpcq::score::W > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "mpcq_score_start: table too large (B x flights x 16)");
+  if (!e->have_traj) return fail(MPCQ_ERR_STATE, "mpcq_score_start needs mpcq_set_trajectories first");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the table that is replaced)
+  Score& sc = e->sc;
+  sc.on = false;
+  auto need = [](auto& buf, size_t elems) {
+    if (buf.grow(elems) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(MPCQ_ERR_DEVICE, "mpcq_score_start: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes");
+  };
+  int rc;
+  if ((rc = need(sc.d_table, (size_t)e->B * flights * mpcq::score::W)) || (rc = need(sc.d_int, (size_t)e->B * 3))) return rc;
+  sc.F = flights; sc.tail_rows = tail_rows;
+  if ((rc = score_init(e))) return rc;
+  sc.on = true;
+  return 0;
+}
+int mpcq_score_get(mpcq_engine* e, double* score, int32_t* flights, int32_t* overflow, int64_t* periods) {
+  ENTER(e);
+  const Score& sc = e->sc;
+  if (!sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_get: no score running");
+  const size_t B = e->B;
+  if (score) HIP_TRY(hipMemcpyAsync(score, sc.d_table.p, B * sc.F * mpcq::score::W * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (flights) HIP_TRY(hipMemcpyAsync(flights, sc.d_int.p + B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (overflow) HIP_TRY(hipMemcpyAsync(overflow, sc.d_int.p + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (periods) *periods = sc.periods;
+  return 0;
+}
+int mpcq_score_clear(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_clear: no score running");
+  return score_init(e);
+}
+int mpcq_score_stop(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_stop: no score running");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the table)
+  e->sc = Score();
   return 0;
 }
 

@@ -54,6 +54,22 @@ LEG_DTYPE = np.dtype([("kind", np.int32), ("reserved", np.int32), ("v_max", np.f
 RECORD_FIELDS = {"x_odom": 1, "x_ref": 2, "w_odom": 4, "x_pred_odom": 8, "cost_solution": 16, "drag": 32, "rgp_mu": 64, "rgp_C": 128,
                  "solver": 256}
 RECORD_DEFAULT = ("x_odom", "x_ref", "w_odom", "x_pred_odom", "cost_solution", "drag", "rgp_mu", "solver")
+# flight scoreboard (include/mpcq.h, mpcq_score_*): the fields of a row in order, and what score_get derives from them
+SCORE_FIELDS = ("steps", "sum_epos2", "sum_evel2", "max_epos2", "sum_rms_pos", "max_v2", "max_vref2", "sum_cost", "tail_steps", "bad_status",
+                "fallbacks", "factorisations", "first_period", "last_period", "rows", "finished")
+SCORE_INT = (0, 8, 9, 10, 11, 12, 13, 14, 15)
+SCORE_DERIVED = ("rmse_pos", "mean_rms_pos", "peak_speed")
+
+
+def score_fields(table):
+    """A score table [..., 16] as a dict of its fields by name (counts and period numbers int64) plus the derived fields."""
+    out = {name: table[..., k].astype(np.int64) if k in SCORE_INT else table[..., k].copy() for k, name in enumerate(SCORE_FIELDS)}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = np.where(out["steps"] > 0, out["steps"], np.nan)
+        out["rmse_pos"] = np.sqrt(out["sum_epos2"] / n)
+        out["mean_rms_pos"] = out["sum_rms_pos"] / n
+        out["peak_speed"] = np.where(out["steps"] > 0, np.sqrt(out["max_v2"]), np.nan)
+    return out
 
 
 class Engine:
@@ -65,6 +81,7 @@ class Engine:
         self._check(self.lib.mpcq_create_sized(ctypes.byref(self._c), ctypes.sizeof(self._c), ctypes.byref(h)))
         self.h = h
         self.B, self.N, self.nb = cfg.batch, cfg.N, cfg.nb
+        self._periods = 0   # periods issued through this handle (what the recorder, a mission and the scoreboard count)
 
     def _check(self, rc):
         if rc != 0:
@@ -187,6 +204,7 @@ class Engine:
         self._check(self.lib.mpcq_mission_set(self.h, _lib.d(wp), wp.shape[1], wp.shape[2], float(v_max), float(a_max), int(order), float(dt),
                                               int(bool(nonlinear)), None if o is None else ctypes.byref(o), _lib.i(leg0)))
         self._mission_legs = wp.shape[1]
+        self._mission_t0 = self._periods
 
     def mission_set_legs(self, legs, wp=None, order=4, dt=0.01, nonlinear=False, opts=None, leg0=None):
         """mission_set with a kind and limits per leg (mpcq_mission_set_legs).  legs: a structured array [B, L] of LEG_DTYPE, or a dict
@@ -217,6 +235,7 @@ class Engine:
         self._check(self.lib.mpcq_mission_set_legs(self.h, legs.ctypes.data_as(ctypes.POINTER(_lib.Leg)), _lib.d(wp), L, n_wp, int(order), float(dt),
                                                    int(bool(nonlinear)), None if o is None else ctypes.byref(o), _lib.i(leg0)))
         self._mission_legs = L
+        self._mission_t0 = self._periods
 
     def mission_get(self):
         """The mission's state: leg [B] (legs consumed), installed [B] (flights installed), last_code [B], leg_code [B, L] (REPLAN_*;
@@ -295,6 +314,65 @@ class Engine:
     def record_stop(self):
         self._check(self.lib.mpcq_record_stop(self.h))
         self._rec = None
+
+    # ---- flight scoreboard: every period folded on the device into the row of the flight the quadrotor is flying, read once
+    def score_start(self, flights, tail_rows=0):
+        """Score every flight from the next period on: `flights` slots per quadrotor, a slot opened by every period whose step used
+        cursor 0; the last `tail_rows` rows of a flight (100: the reference's dropped last second) and the periods beyond its end count
+        as tail_steps only.  Replaces a running score."""
+        self._check(self.lib.mpcq_score_start(self.h, int(flights), int(tail_rows)))
+        self._score_flights = int(flights)
+        self._score_t0 = self._periods
+
+    def score_get(self):
+        """The scoreboard: the sixteen fields of include/mpcq.h by name, each [B, F] (fields 0 and 8..15 int64), flights [B] (slots that
+        hold a period), overflow [B] (periods that found no slot), periods, and the derived rmse_pos = sqrt(sum_epos2 / steps),
+        mean_rms_pos = sum_rms_pos / steps (the ordinate of the reference's compare_trajectories scatter) and peak_speed = sqrt(max_v2)
+        (its abscissa), NaN where steps == 0."""
+        F = getattr(self, "_score_flights", None)
+        if F is None:
+            raise _lib.MpcqError("score_get needs score_start first")
+        B = self.B
+        t = np.zeros((B, F, len(SCORE_FIELDS)))
+        out = dict(flights=np.zeros(B, np.int32), overflow=np.zeros(B, np.int32))
+        periods = ctypes.c_int64()
+        self._check(self.lib.mpcq_score_get(self.h, _lib.d(t), _lib.i(out["flights"]), _lib.i(out["overflow"]), ctypes.byref(periods)))
+        out["periods"] = periods.value
+        out.update(score_fields(t))
+        return out
+
+    def score_clear(self):
+        """Table, slots, overflow and the period count back to their start values; the score stays on."""
+        self._check(self.lib.mpcq_score_clear(self.h))
+        self._score_t0 = self._periods
+
+    def score_stop(self):
+        self._check(self.lib.mpcq_score_stop(self.h))
+        self._score_flights = None
+
+    def mission_scores(self):
+        """The scoreboard by mission leg: the fields of score_get as [B, L].  Leg l of quadrotor b, installed (leg_code REPLAN_DONE) in
+        period p, is the slot whose first_period is p + 1; a leg that was not installed, has not begun or was lost to overflow gives NaN
+        (float fields) or -1 (integer fields).  Needs score and mission to count the same periods -- score_start / score_clear and
+        mission_set* with no period between them -- else ValueError.  The check rests on this handle's own count of the periods it
+        issued (step, step_device_async, sim_steps, sim_control_periods; the library does not report a mission's period count): it does
+        not see periods issued on the same engine through the C ABI or another wrapper, nor those of a call that failed part-way; after
+        either, start score and mission again before relying on the mapping."""
+        if getattr(self, "_score_flights", None) is None or getattr(self, "_mission_legs", None) is None:
+            raise ValueError("mission_scores needs a running score and a mission")
+        if self._score_t0 != self._mission_t0:   # (periods issued through this handle, counted by step, sim_steps and their like)
+            raise ValueError("mission_scores: score and mission do not count the same periods (score_start / score_clear and mission_set* "
+                             "with no period between them)")
+        sc, ms = self.score_get(), self.mission_get()
+        want = np.where(ms["leg_code"] == REPLAN_DONE, ms["leg_period"].astype(np.int64) + 1, -2)            # [B, L]
+        first = np.where(sc["steps"] + sc["tail_steps"] > 0, sc["first_period"], -1)                          # [B, F]
+        hit = want[:, :, None] == first[:, None, :]                                                           # [B, L, F]
+        found, slot = hit.any(axis=2), hit.argmax(axis=2)
+        out = {}
+        for name in SCORE_FIELDS + SCORE_DERIVED:
+            v = np.take_along_axis(sc[name], slot, axis=1)
+            out[name] = np.where(found, v, -1 if v.dtype.kind == "i" else np.nan)
+        return out
 
     def set_reference(self, yref, yrefN):
         yref = self._f(yref, (self.B, self.N, NY))
@@ -435,6 +513,7 @@ class Engine:
         w = np.zeros((self.B, NU))
         xp = np.zeros((self.B, NX))
         self._check(self.lib.mpcq_step(self.h, _lib.d(x), _lib.d(w), _lib.d(xp)))
+        self._periods += 1
         return w, xp
 
     def sim_reset(self, x0):
@@ -443,6 +522,7 @@ class Engine:
 
     def sim_steps(self, K, n_sub, sim_dt=5e-3):
         self._check(self.lib.mpcq_sim_steps(self.h, int(K), int(n_sub), float(sim_dt)))
+        self._periods += max(int(K), 0)
 
     def sim_run(self, K, n_sub, sim_dt=5e-3):
         """K closed-loop periods in one launch, every instance advancing on its own (same results as sim_steps)."""
@@ -484,11 +564,13 @@ class Engine:
     def sim_control_periods(self, K, control_dt, sim_dt=5e-3):
         n = ctypes.c_int32()
         self._check(self.lib.mpcq_sim_control_periods(self.h, int(K), float(control_dt), float(sim_dt), ctypes.byref(n)))
+        self._periods += max(int(K), 0)
         return n.value
 
     def step_device_async(self, d_x_meas: int, d_w_out: int = 0):
         """Fused step on float64 device buffers (raw device addresses); asynchronous on the engine's stream."""
         self._check(self.lib.mpcq_step_device_async(self.h, ctypes.c_void_p(d_x_meas), ctypes.c_void_p(d_w_out or None)))
+        self._periods += 1
 
     def synchronize(self):
         self._check(self.lib.mpcq_synchronize(self.h))
