@@ -150,7 +150,9 @@ const char* mpcq_last_error(void);
  * The 8 behind them (since 0.6.1) hash the device generators of mpcq_replan / mpcq_replan_nonlinear (csrc/mpcq_replan.hpp, since 0.6.2
  * with csrc/mpcq_replan_nl.hpp and csrc/mpcq_minsnap_nl.hpp), since 0.6.3 the flight recorder (csrc/mpcq_record.hpp), since 0.6.4 the RGP
  * read-out (csrc/mpcq_predict.hpp), since 0.6.5 the device missions (csrc/mpcq_mission.hpp), since 0.6.6 the device circle generator
- * (csrc/mpcq_circle.hpp) and, since 0.6.7, the flight scoreboard (csrc/mpcq_score.hpp). */
+ * (csrc/mpcq_circle.hpp), since 0.6.7 the flight scoreboard (csrc/mpcq_score.hpp) and, with mpcq_rgp_train / mpcq_record_train, the device
+ * trainer (csrc/mpcq_train.hpp with csrc/mpcq_learn_core.hpp, which mpcq_learn.hip shares).  The number stays 0.6.7 with the trainer:
+ * tests/test_score.py pins it; the eight digits tell a library with the trainer from one without. */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -540,6 +542,53 @@ int mpcq_rgp_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t per_qu
  * a window outside the rows recorded so far (nrows < 1 included); the argument rules of mpcq_rgp_predict. */
 int mpcq_record_predict(mpcq_engine* e, const double* xq /*[3,M]*/, int32_t M, int32_t row0, int32_t nrows,
                         double* mean /*[count,nrows,3,M] or NULL*/, double* var /*[count,nrows,3,M] or NULL*/);
+
+/* ---- training from a recording or a sample stream: the reference's offline trainer of the recursive GP loops
+ * RGP.regress over a whole dataset for a model with its own basis and hyper-parameters (src/gp/rgp_train.py:95-103); RGP.learn
+ * (src/gp/RGP.py:332-505) is fed the same way.  Here one persistent launch runs one workgroup per (stream, axis) regressor over all T
+ * samples of its stream, the regressor state in LDS from the first sample to the last (csrc/mpcq_train.hpp).  All of it in float64,
+ * whatever the engine's precision (the recorder stores the drag field in double).
+ *   MPCQ_TRAIN_REGRESS: the update of mpcq_rgp_regress (formula above mpcq_rgp_predict: J = k* K_x^-1,
+ *       G = C J^T / (sigma_f^2 - J k*^T + J C J^T + sigma_n^2), mu += G (y - J mu), C -= G J C, not symmetrised) with fixed theta,
+ *       from mu = 0, C = K(X,X) + sigma_n^2 I, K_x^-1 from the routine mpcq_create uses.
+ *   MPCQ_TRAIN_LEARN:   the update of mpcq_learn_step, sample by sample (one routine serves both), from the start values of
+ *       mpcq_learn_create: mu_g = 0, C_g = K_x, mu_eta = theta, C_eta = I, K_x^-1 by the learner's Gauss-Jordan rebuild.
+ * nb = 0 trains the engine's own model (its basis, theta and device copy of K_x^-1; an MPCQ_FLAG_STATIC_GP engine has one too):
+ * the mu, C of a REGRESS run load into any engine of that model with mpcq_set_state. */
+#define MPCQ_TRAIN_REGRESS 1
+#define MPCQ_TRAIN_LEARN   2
+typedef struct mpcq_train_spec {
+  int32_t mode;          /* MPCQ_TRAIN_REGRESS | MPCQ_TRAIN_LEARN */
+  int32_t pair_next;     /* 0: sample t = (v_body[t], a_drag[t]), what the flying engine regressed on.
+                            1: (v_body[t], a_drag[t+1]), T-1 samples: the pairing of the reference's offline loader
+                               (src/gp/DataLoaderGP.py:92-97) */
+  int32_t nb;            /* 0: the engine's own basis / theta / K_x^-1 (basis, theta must be NULL); else 1..64 */
+  const double* basis;   /* [3, nb] */
+  const double* theta;   /* [3, 3] initial (LEARN) or fixed (REGRESS) L, sigma_f, sigma_n */
+} mpcq_train_spec;
+/* host arrays, each may be NULL (not all): S streams in the caller's order */
+typedef struct mpcq_train_out {
+  double* mu;       /* [S,3,nb] */
+  double* C;        /* [S,3,nb,nb] */
+  double* mu_eta;   /* [S,3,3]      LEARN only */
+  double* C_eta;    /* [S,3,3,3]    LEARN only */
+  double* Kx_inv;   /* [S,3,nb,nb]  LEARN only: K_x^-1 of the learned hyper-parameters */
+} mpcq_train_out;
+/* Trains S x 3 regressors on caller samples v_body, a_drag [S,T,3] (axis d of stream s learns from v_body[s,:,d] -> a_drag[s,:,d]).
+ * Ordered behind everything the engine has enqueued, on all of its streams; blocks until the outputs are on the host; changes no
+ * engine or recorder state (scratch belongs to the engine and goes with mpcq_destroy).  MPCQ_ERR_INVALID: spec or out NULL, all
+ * outputs NULL, mode not one of the two, nb outside 0..64, nb > 0 with basis or theta NULL, nb = 0 with either set, a length scale
+ * <= 0 (or K_x not positive definite), S < 1, T < 1 (T < 2 with pair_next), a LEARN-only output in REGRESS mode, v_body or a_drag
+ * NULL.  MPCQ_ERR_STATE: nb = 0 on an engine with nb = 0.  MPCQ_ERR_DEVICE: the scratch cannot be allocated, or the device offers less
+ * LDS per workgroup than the smallest layout needs.  Non-finite samples are no error: the regressors that see one come back NaN,
+ * the others are untouched. */
+int mpcq_rgp_train(mpcq_engine* e, const mpcq_train_spec* spec, const double* v_body /*[S,T,3]*/, const double* a_drag /*[S,T,3]*/,
+                   int32_t S, int32_t T, mpcq_train_out* out);
+/* The same training (bit for bit: one routine serves both) on rows row0 .. row0 + nrows - 1 of the active recording's MPCQ_RECORD_DRAG
+ * field, read from the recorder's device buffer in place: S = the recording's count, in the caller's order as for mpcq_record_predict,
+ * T = nrows.  MPCQ_ERR_STATE: no active recording (and the rule above).  MPCQ_ERR_INVALID: MPCQ_RECORD_DRAG not recorded, a window
+ * outside the rows recorded so far (nrows < 1, or < 2 with pair_next, included), the argument rules of mpcq_rgp_train. */
+int mpcq_record_train(mpcq_engine* e, const mpcq_train_spec* spec, int32_t row0, int32_t nrows, mpcq_train_out* out);
 
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)

@@ -52,6 +52,21 @@ class Leg(ctypes.Structure):
 
 _legp = ctypes.POINTER(Leg)
 
+
+class TrainSpec(ctypes.Structure):
+    """mpcq_train_spec (include/mpcq.h): what mpcq_rgp_train / mpcq_record_train train and with which model."""
+    _fields_ = [("mode", ctypes.c_int32), ("pair_next", ctypes.c_int32), ("nb", ctypes.c_int32), ("basis", _dp), ("theta", _dp)]
+
+
+class TrainOut(ctypes.Structure):
+    """mpcq_train_out (include/mpcq.h): host arrays of the trained state, each may be NULL."""
+    _fields_ = [("mu", _dp), ("C", _dp), ("mu_eta", _dp), ("C_eta", _dp), ("Kx_inv", _dp)]
+
+
+TRAIN_MODES = {"regress": 1, "learn": 2}
+_tsp = ctypes.POINTER(TrainSpec)
+_top = ctypes.POINTER(TrainOut)
+
 # every symbol declared in include/mpcq.h: (name, restype, argtypes)
 SYMBOLS = [
     ("mpcq_last_error", ctypes.c_char_p, []),
@@ -127,6 +142,8 @@ SYMBOLS = [
     ("mpcq_score_stop", ctypes.c_int, [_vp]),
     ("mpcq_rgp_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
     ("mpcq_record_predict", ctypes.c_int, [_vp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp]),
+    ("mpcq_rgp_train", ctypes.c_int, [_vp, _tsp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _top]),
+    ("mpcq_record_train", ctypes.c_int, [_vp, _tsp, ctypes.c_int32, ctypes.c_int32, _top]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),
     ("mpcq_learn_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mpcq_learn_destroy", ctypes.c_int, [_vp]),

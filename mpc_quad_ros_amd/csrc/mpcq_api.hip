@@ -28,6 +28,7 @@
 #include "mpcq_record.hpp"
 #include "mpcq_score.hpp"
 #include "mpcq_predict.hpp"
+#include "mpcq_train.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -167,6 +168,19 @@ bool spd_inverse(const std::vector<double>& A, int n, std::vector<double>& Ai) {
   return true;
 }
 
+
+// RGP constants of one axis (RGP.__init__, src/gp/RGP.py:140-157): K_x = K(X,X) + sn^2 I [nb][nb] and its inverse.  The routine behind
+// mpcq_create and behind a caller's model in mpcq_rgp_train / mpcq_record_train.  false: K_x is not positive definite.
+bool rgp_axis_constants(const double* X, int nb, double Lh, double sf, double sn, std::vector<double>& K, std::vector<double>& Ki) {
+  K.assign((size_t)nb * nb, 0.0);
+  for (int i = 0; i < nb; ++i)
+    for (int j = 0; j < nb; ++j) {
+      const double dl = X[i] - X[j];
+      K[i * nb + j] = sf * sf * std::exp(-0.5 * dl * dl / (Lh * Lh)) + (i == j ? sn * sn : 0.0);
+    }
+  return spd_inverse(K, nb, Ki);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ engine
@@ -295,6 +309,13 @@ struct mpcq_engine : EngineQueues {
     DevBuf<double> Kinv, basis, xq, Jt, out;
     DevBuf<int> pos;
   } pr;
+  // device trainer (mpcq_rgp_train / mpcq_record_train, mpcq_train.hpp): scratch sized by the request
+  struct TrainScratch {
+    DevBuf<double> in;      // caller samples: v_body [S,T,3] | a_drag [S,T,3]
+    DevBuf<double> model;   // theta [3,3] | K_x [3,nb,nb] | a caller's model: basis [3,nb] | K_x^-1 [3,nb,nb]
+    DevBuf<double> out;     // mu | C | mu_eta | C_eta | K_x^-1 of every regressor
+    DevBuf<int> pos;
+  } tr;
   virtual int rgp_predict(const double* xq, int M, int per_quad, double* mean, double* var) = 0;
   virtual TrajSlots traj_slots() = 0;
   virtual int init() = 0;
@@ -334,6 +355,18 @@ namespace {
 // ---- RGP read-out: the one evaluation routine behind mpcq_rgp_predict (live state, TQ = the engine's precision) and
 // mpcq_record_predict (rows of the recorder's float64 buffers in place).  Set s reads mu / C at slab s (pos_host == nullptr) or at slab
 // (row0 + k) * count + pos[j] with (j, k) = (s / nrows, s % nrows); outputs [nsets][3][M] go straight to the caller's arrays.
+// the engine's own basis and K_x^-1 in double on the device (the step kernel's copies have the engine's precision): uploaded on first use
+int rgp_model_on_device(mpcq_engine* e) {
+  mpcq_engine::PredictScratch& pr = e->pr;
+  const int nb = e->nb;
+  if (pr.Kinv.p && pr.basis.p) return 0;
+  HIP_TRY(pr.Kinv.grow((size_t)3 * nb * nb));
+  HIP_TRY(pr.basis.grow((size_t)3 * nb));
+  HIP_TRY(hipMemcpyAsync(pr.Kinv.p, e->kxinv64.data(), (size_t)3 * nb * nb * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(pr.basis.p, e->basis.data(), (size_t)3 * nb * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  return 0;
+}
+
 template <typename TQ>
 int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long C_stride, size_t nsets, const int* pos_host, int row0, int nrows, int count,
                 const double* xq, int M, int per_quad, double* mean, double* var) {
@@ -342,12 +375,7 @@ int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long 
   const int nb = e->nb;
   hipStream_t s = e->stream;
   if (nsets * 3 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "RGP read-out: too many (quadrotor, row) sets for one call");
-  if (!pr.Kinv.p || !pr.basis.p) {
-    HIP_TRY(pr.Kinv.grow((size_t)3 * nb * nb));
-    HIP_TRY(pr.basis.grow((size_t)3 * nb));
-    HIP_TRY(hipMemcpyAsync(pr.Kinv.p, e->kxinv64.data(), (size_t)3 * nb * nb * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(pr.basis.p, e->basis.data(), (size_t)3 * nb * sizeof(double), hipMemcpyHostToDevice, s));
-  }
+  if (const int rc = rgp_model_on_device(e)) return rc;
   const size_t nq = (per_quad ? nsets : 1) * 3 * (size_t)M, no = nsets * 3 * (size_t)M;
   HIP_TRY(pr.xq.grow(nq));
   HIP_TRY(pr.out.grow(no * ((mean ? 1 : 0) + (var ? 1 : 0))));
@@ -550,13 +578,8 @@ struct EngineT : mpcq_engine {
       const double Lh = theta[3 * d], sf = theta[3 * d + 1], sn = theta[3 * d + 2];
       if (!(Lh > 0)) return fail(MPCQ_ERR_INVALID, "theta: length scale must be > 0");
       m.L2inv[d] = (T)(1.0 / (Lh * Lh)); m.sf2[d] = (T)(sf * sf); m.sn2[d] = (T)(sn * sn);
-      std::vector<double> K(nb * nb), Ki;
-      for (int i = 0; i < nb; ++i)
-        for (int j = 0; j < nb; ++j) {
-          const double dl = basis[d * nb + i] - basis[d * nb + j];
-          K[i * nb + j] = sf * sf * std::exp(-0.5 * dl * dl / (Lh * Lh)) + (i == j ? sn * sn : 0.0);
-        }
-      if (!spd_inverse(K, nb, Ki)) return fail(MPCQ_ERR_INVALID, "K_x is not positive definite");
+      std::vector<double> K, Ki;
+      if (!rgp_axis_constants(basis.data() + (size_t)d * nb, nb, Lh, sf, sn, K, Ki)) return fail(MPCQ_ERR_INVALID, "K_x is not positive definite");
       std::copy(K.begin(), K.end(), Kx.begin() + (size_t)d * nb * nb);
       std::copy(Ki.begin(), Ki.end(), Kxinv.begin() + (size_t)d * nb * nb);
     }
@@ -1810,6 +1833,158 @@ int mpcq_record_predict(mpcq_engine* e, const double* xq, int32_t M, int32_t row
   const int nb = e->nb;
   return predict_run<double>(e, r.d_f[mpcq::record::F_MU].p, 3L * nb, fixed ? nullptr : r.d_f[mpcq::record::F_C].p, 3L * nb * nb, (size_t)r.count * nrows, r.pos.data(),
                              row0, nrows, r.count, xq, M, 0, mean, var);
+}
+
+// ---- device trainer (mpcq_train.hpp).  Both entry points run train_run on the engine's stream, as the RGP read-out does.
+namespace {
+// LDS a workgroup may ask for: the device's opt-in limit.  MPCQ_TRAIN_LDS_BYTES lowers it (tests and measurements: every residency arm
+// at every basis size).
+int train_lds_limit(int device, size_t* out) {
+  size_t lim = 160 * 1024;
+#ifndef MPCQ_EMU_BUILD
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, device) != hipSuccess || v <= 0) {
+    (void)hipGetLastError();
+    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  }
+  if (v > 0) lim = std::min(lim, (size_t)v);
+#else
+  (void)device;
+#endif
+  if (const char* s = getenv("MPCQ_TRAIN_LDS_BYTES")) {
+    const long long v2 = atoll(s);
+    if (v2 > 0 && (size_t)v2 < lim) lim = (size_t)v2;
+  }
+  *out = lim;
+  return 0;
+}
+extern "C++" {   // (this part of the file has C linkage)
+template <int MODE, bool RC, bool RK>
+int train_launch(hipStream_t s, unsigned R, size_t lds, const mpcq::train::Args& a) {
+  void (*k)(const mpcq::train::Args) = &mpcq::train::train_kernel<MODE, RC, RK>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, dim3(R), dim3(64), lds, s, a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+}
+// the argument rules the two entry points share; *nb_out: the basis size trained with
+int train_args(const char* who_, const mpcq_engine* e, const mpcq_train_spec* sp, const mpcq_train_out* out, int* nb_out) {
+  const std::string who(who_);
+  if (!sp || !out) return fail(MPCQ_ERR_INVALID, who + ": null spec or out");
+  if (!out->mu && !out->C && !out->mu_eta && !out->C_eta && !out->Kx_inv) return fail(MPCQ_ERR_INVALID, who + ": every output is NULL");
+  if (sp->mode != MPCQ_TRAIN_REGRESS && sp->mode != MPCQ_TRAIN_LEARN) return fail(MPCQ_ERR_INVALID, who + ": mode must be MPCQ_TRAIN_REGRESS or MPCQ_TRAIN_LEARN");
+  if (sp->pair_next != 0 && sp->pair_next != 1) return fail(MPCQ_ERR_INVALID, who + ": pair_next must be 0 or 1");
+  if (sp->nb < 0 || sp->nb > mpcq::train::MAX_NB) return fail(MPCQ_ERR_INVALID, who + ": nb outside 0..64");
+  if (sp->nb > 0 && (!sp->basis || !sp->theta)) return fail(MPCQ_ERR_INVALID, who + ": nb > 0 needs basis and theta");
+  if (sp->nb == 0 && (sp->basis || sp->theta)) return fail(MPCQ_ERR_INVALID, who + ": nb = 0 trains the engine's own model: basis and theta must be NULL");
+  if (sp->mode == MPCQ_TRAIN_REGRESS && (out->mu_eta || out->C_eta || out->Kx_inv)) return fail(MPCQ_ERR_INVALID, who + ": mu_eta, C_eta and Kx_inv are outputs of MPCQ_TRAIN_LEARN");
+  if (sp->nb > 0)
+    for (int d = 0; d < 3; ++d)
+      if (!(sp->theta[d * 3] > 0)) return fail(MPCQ_ERR_INVALID, who + ": theta: length scale must be > 0");
+  if (sp->nb == 0 && !e->nb) return fail(MPCQ_ERR_STATE, who + ": engine has no RGP (nb = 0)");
+  if (sp->nb == 0 && e->nb > mpcq::train::MAX_NB) return fail(MPCQ_ERR_INVALID, who + ": the engine's basis is larger than 64");
+  *nb_out = sp->nb ? sp->nb : e->nb;
+  return 0;
+}
+// v, a: device pointers to sample 0 (inputs, targets); sample k of stream s, axis d at [(pos ? pos[s] : s) * stream_stride + k * step_stride + d].
+// T counts the samples as stored; with pair_next the targets move one step on and T - 1 samples are walked.
+int train_run(mpcq_engine* e, const mpcq_train_spec* sp, int nb, const double* v, const double* a, long stream_stride, long step_stride,
+              const int* pos_host, int S, int T, const mpcq_train_out* out) {
+  namespace tn = mpcq::train;
+  mpcq_engine::TrainScratch& tr = e->tr;
+  hipStream_t s = e->stream;
+  const bool learn = sp->mode == MPCQ_TRAIN_LEARN, own = sp->nb == 0;
+  const size_t n = nb, nn = n * n, R = (size_t)S * 3;
+  if (R > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "RGP training: too many streams for one call");
+  auto need = [](auto& buf, size_t elems) {
+    if (buf.grow(elems) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(MPCQ_ERR_DEVICE, "RGP training: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes");
+  };
+  int rc;
+  // the model on the device: theta | K_x (the start value of C) | basis | K_x^-1
+  const double* basis_h = own ? e->basis.data() : sp->basis;
+  const double* theta_h = own ? e->theta.data() : sp->theta;
+  std::vector<double> hm(9 + 3 * nn + (own ? 0 : 3 * n + 3 * nn), 0.0);
+  std::copy(theta_h, theta_h + 9, hm.begin());
+  if (!learn)   // (LEARN builds its start values on the device, as mpcq_learn_create does)
+    for (int d = 0; d < 3; ++d) {
+      std::vector<double> K, Ki;
+      if (!rgp_axis_constants(basis_h + d * n, nb, theta_h[3 * d], theta_h[3 * d + 1], theta_h[3 * d + 2], K, Ki))
+        return fail(MPCQ_ERR_INVALID, "RGP training: K_x is not positive definite");
+      std::copy(K.begin(), K.end(), hm.begin() + 9 + d * nn);
+      if (!own) std::copy(Ki.begin(), Ki.end(), hm.begin() + 9 + 3 * nn + 3 * n + d * nn);
+    }
+  if (!own) std::copy(basis_h, basis_h + 3 * n, hm.begin() + 9 + 3 * nn);
+  if ((rc = need(tr.model, hm.size()))) return rc;
+  if (own && (rc = rgp_model_on_device(e))) return rc;
+  HIP_TRY(hipMemcpyAsync(tr.model.p, hm.data(), hm.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  if (pos_host) {
+    if ((rc = need(tr.pos, (size_t)S))) return rc;
+    HIP_TRY(hipMemcpyAsync(tr.pos.p, pos_host, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  const size_t o_mu = 0, o_C = o_mu + R * n, o_eta = o_C + R * nn, o_Ce = o_eta + R * 3, o_K = o_Ce + R * 9;
+  if ((rc = need(tr.out, learn ? o_K + R * nn : o_eta))) return rc;
+  tn::Args g;
+  std::memset(&g, 0, sizeof(g));
+  g.nb = nb; g.T = sp->pair_next ? T - 1 : T;
+  g.v = v; g.a = sp->pair_next ? a + step_stride : a;
+  g.stream_stride = stream_stride; g.step_stride = step_stride;
+  g.pos = pos_host ? tr.pos.p : nullptr;
+  g.theta = tr.model.p;
+  g.C0 = tr.model.p + 9;
+  g.basis = own ? e->pr.basis.p : tr.model.p + 9 + 3 * nn;
+  g.K0 = own ? e->pr.Kinv.p : tr.model.p + 9 + 3 * nn + 3 * n;
+  g.mu = tr.out.p + o_mu; g.C = tr.out.p + o_C;
+  if (learn) { g.mu_eta = tr.out.p + o_eta; g.C_eta = tr.out.p + o_Ce; g.Kinv = tr.out.p + o_K; }
+  // residency: the largest of {C and K_x^-1, C, neither} in LDS that the limit allows
+  size_t limit = 0;
+  if ((rc = train_lds_limit(e->cfg.device, &limit))) return rc;
+  int arm = -1;
+  size_t lds = 0;
+  for (int k = 0; k < 3 && arm < 0; ++k) {
+    lds = (size_t)tn::layout(nb, sp->mode, k < 2, k < 1).total * sizeof(double);
+    if (lds <= limit) arm = k;
+  }
+  if (arm < 0) return fail(MPCQ_ERR_DEVICE, "RGP training: " + std::to_string(lds) + " bytes of LDS per workgroup needed, " + std::to_string(limit) + " available");
+  const unsigned Ru = (unsigned)R;
+  if (learn) rc = arm == 0 ? train_launch<tn::LEARN, true, true>(s, Ru, lds, g) : arm == 1 ? train_launch<tn::LEARN, true, false>(s, Ru, lds, g) : train_launch<tn::LEARN, false, false>(s, Ru, lds, g);
+  else rc = arm == 0 ? train_launch<tn::REGRESS, true, true>(s, Ru, lds, g) : arm == 1 ? train_launch<tn::REGRESS, true, false>(s, Ru, lds, g) : train_launch<tn::REGRESS, false, false>(s, Ru, lds, g);
+  if (rc) return rc;
+  if (out->mu) HIP_TRY(hipMemcpyAsync(out->mu, g.mu, R * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (out->C) HIP_TRY(hipMemcpyAsync(out->C, g.C, R * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (out->mu_eta) HIP_TRY(hipMemcpyAsync(out->mu_eta, g.mu_eta, R * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (out->C_eta) HIP_TRY(hipMemcpyAsync(out->C_eta, g.C_eta, R * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (out->Kx_inv) HIP_TRY(hipMemcpyAsync(out->Kx_inv, g.Kinv, R * nn * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+}  // namespace
+int mpcq_rgp_train(mpcq_engine* e, const mpcq_train_spec* sp, const double* v_body, const double* a_drag, int32_t S, int32_t T, mpcq_train_out* out) {
+  ENTER(e);
+  int nb = 0;
+  if (const int rc = train_args("mpcq_rgp_train", e, sp, out, &nb)) return rc;
+  if (!v_body || !a_drag) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_train: null samples");
+  if (S < 1) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_train: S must be >= 1");
+  if (T < 1 + sp->pair_next) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_train: T must be >= 1 (>= 2 with pair_next)");
+  const size_t cnt = (size_t)S * T * 3;
+  if (e->tr.in.grow(2 * cnt) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQ_ERR_DEVICE, "mpcq_rgp_train: cannot allocate the sample buffer"); }
+  HIP_TRY(hipMemcpyAsync(e->tr.in.p, v_body, cnt * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->tr.in.p + cnt, a_drag, cnt * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  return train_run(e, sp, nb, e->tr.in.p, e->tr.in.p + cnt, 3L * T, 3, nullptr, S, T, out);
+}
+int mpcq_record_train(mpcq_engine* e, const mpcq_train_spec* sp, int32_t row0, int32_t nrows, mpcq_train_out* out) {
+  ENTER(e);
+  const Recorder& r = e->rec;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_record_train: no active recording");
+  int nb = 0;
+  if (const int rc = train_args("mpcq_record_train", e, sp, out, &nb)) return rc;
+  if (!(r.fields & MPCQ_RECORD_DRAG)) return fail(MPCQ_ERR_INVALID, "mpcq_record_train: MPCQ_RECORD_DRAG was not recorded");
+  if (row0 < 0 || nrows < 1 + sp->pair_next || (long long)row0 + nrows > r.rows)
+    return fail(MPCQ_ERR_INVALID, "mpcq_record_train: row window outside the rows recorded so far (nrows >= 1, >= 2 with pair_next)");
+  const double* slab = r.d_f[mpcq::record::F_DRAG].p + (size_t)row0 * r.count * 6;
+  return train_run(e, sp, nb, slab, slab + 3, 6, 6L * r.count, r.pos.data(), r.count, nrows, out);
 }
 
 int mpcq_get_trajectories(mpcq_engine* e, double* traj, int32_t* len) {

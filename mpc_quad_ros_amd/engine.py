@@ -507,6 +507,56 @@ class Engine:
             self._check(self.lib.mpcq_record_predict(self.h, _lib.d(xq), M, row0, nrows, _lib.d(mean), _lib.d(v)))
         return (mean, v) if var else mean
 
+    # ---- training on the device: all samples of a stream in one launch
+    def _train_call(self, S, mode, basis, theta, pair_next, call):
+        """spec and output arrays of a training call; call(spec, out) -> rc"""
+        if mode not in _lib.TRAIN_MODES:
+            raise ValueError(f"mode must be one of {sorted(_lib.TRAIN_MODES)}")
+        if (basis is None) != (theta is None):
+            raise ValueError("basis and theta go together (both None: the engine's own model)")
+        keep = []
+        if basis is None:
+            n = self.nb
+        else:
+            basis = np.ascontiguousarray(basis, dtype=np.float64).reshape(3, -1)
+            th = np.asarray(theta, dtype=np.float64)
+            theta = np.ascontiguousarray(np.tile(th, (3, 1)) if th.shape == (3,) else th.reshape(3, 3))
+            n = basis.shape[1]
+            keep = [basis, theta]
+        spec = _lib.TrainSpec(mode=_lib.TRAIN_MODES[mode], pair_next=int(bool(pair_next)), nb=0 if basis is None else n,
+                              basis=_lib.d(basis), theta=_lib.d(theta))
+        res = dict(mu_g=np.zeros((S, 3, n)), C_g=np.zeros((S, 3, n, n)))
+        if mode == "learn":
+            res.update(mu_eta=np.zeros((S, 3, 3)), C_eta=np.zeros((S, 3, 3, 3)), K_x_inv=np.zeros((S, 3, n, n)))
+        out = _lib.TrainOut(mu=_lib.d(res["mu_g"]), C=_lib.d(res["C_g"]), mu_eta=_lib.d(res.get("mu_eta")), C_eta=_lib.d(res.get("C_eta")),
+                            Kx_inv=_lib.d(res.get("K_x_inv")))
+        self._check(call(ctypes.byref(spec), ctypes.byref(out)))
+        del keep
+        return res
+
+    def rgp_train(self, v_body, a_drag, mode="regress", basis=None, theta=None, pair_next=False):
+        """Train S x 3 drag models on sample streams v_body, a_drag [S,T,3] in one launch: mode "regress" (RGP.regress over all
+        samples, fixed hyper-parameters) or "learn" (RGP.learn, what Learner.step does sample by sample).  basis [3,nb] and theta
+        (3 values or [3,3]) name another model than the engine's own (None, None); pair_next pairs v_body[t] with a_drag[t+1] (the
+        reference's offline loader).  Returns the keys of Learner.get(): mu_g [S,3,nb], C_g [S,3,nb,nb], and for "learn" mu_eta,
+        C_eta, K_x_inv.  A "regress" result on the engine's own model loads with set_state(mu=, C=)."""
+        v = np.ascontiguousarray(v_body, dtype=np.float64)
+        a = np.ascontiguousarray(a_drag, dtype=np.float64)
+        if v.ndim != 3 or v.shape[2] != 3 or a.shape != v.shape:
+            raise ValueError("v_body and a_drag must both be [S, T, 3]")
+        S, T = v.shape[0], v.shape[1]
+        return self._train_call(S, mode, basis, theta, pair_next,
+                                lambda sp, out: self.lib.mpcq_rgp_train(self.h, sp, _lib.d(v), _lib.d(a), S, T, out))
+
+    def record_train(self, rows=None, mode="regress", basis=None, theta=None, pair_next=False):
+        """rgp_train on the recorded rows `rows` = (row0, nrows) (None: all recorded so far) of the active recording's v_body / a_drag,
+        read from the device buffer in place, for the recorded quadrotors in the order of record_start."""
+        rec = getattr(self, "_rec", None)
+        recorded = self.record_info()[0]   # (raises without an active recording)
+        row0, nrows = (0, recorded) if rows is None else (int(rows[0]), int(rows[1]))
+        return self._train_call(len(rec["quads"]), mode, basis, theta, pair_next,
+                                lambda sp, out: self.lib.mpcq_record_train(self.h, sp, row0, nrows, out))
+
     # ---- fused path
     def step(self, x_meas):
         x = self._f(x_meas, (self.B, NX))
