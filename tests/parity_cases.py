@@ -190,12 +190,14 @@ def case_free_running_log(make_engine, name, K, precision=0):
     return worst
 
 
-def case_explicit_api(make_engine, B=4, N=10, nb=10, precision=0, seed=0):
-    """acados-style path: set_reference / set_params / solve / get, predict_nominal, rgp_regress."""
+def case_explicit_api(make_engine, B=4, N=10, nb=10, precision=0, seed=0, skip=None, basis_vmax=12.0):
+    """acados-style path: set_reference / set_params / solve / get, predict_nominal, rgp_regress.
+    skip: control_freq_factor (default: the node's int((T / N) / 0.01), which is 0 -- refused -- beyond N = 100).
+    basis_vmax: the basis points span [-basis_vmax, basis_vmax] (the node's 12 m/s puts most of them where these states never fly)."""
     rng = np.random.default_rng(seed)
-    kw = dict(batch=B, N=N, T=1.0, quad=hummingbird(), nb=nb, dt_pred=0.01)
+    kw = dict(batch=B, N=N, T=1.0, quad=hummingbird(), nb=nb, dt_pred=0.01, skip=skip)
     if nb:
-        kw.update(basis=rgp_basis_linspace(12.0, nb), theta=[1.0, 0.1, 0.1])
+        kw.update(basis=rgp_basis_linspace(basis_vmax, nb), theta=[1.0, 0.1, 0.1])
     e, o = make_engine(EngineConfig(precision=precision, **kw)), OracleEngine(EngineConfig(**kw))
     x0 = random_states(rng, B, 0.3)
     xr = random_states(rng, B, 0.3)
@@ -227,17 +229,18 @@ def case_explicit_api(make_engine, B=4, N=10, nb=10, precision=0, seed=0):
         assert rel_err(C_e, C_o, 1e-2) < (1e-11 if precision == 0 else 1e-4)
 
 
-def case_swarm_closed_loop(make_engine, B, N, nb, K, precision=0, seed=1, plant_sub=2, start=0, min_changes=0, teacher=None):
+def case_swarm_closed_loop(make_engine, B, N, nb, K, precision=0, seed=1, plant_sub=2, start=0, min_changes=0, teacher=None, skip=None):
     """Synthetic random-waypoint swarm (the bench workload family), host-driven closed loop with the
     oracle's drag plant; engine and oracle free-running side by side on identical measurements.
     start > 0: the run begins `start` samples into the references, on the reference state, with a cold iterate
     (interior-point solves first, then a fast stretch where inputs saturate); min_changes: quadrotor-steps that must
     have gone through more than one working set.
     teacher (default: on for f32): the engine's state is overwritten with the oracle's before every step, so every solve is
-    judged on its own.  Every solve of either precision has to report status 0; returns the worst per-quadrotor deviation."""
+    judged on its own.  Every solve of either precision has to report status 0; returns the worst per-quadrotor deviation.
+    skip: as in case_explicit_api."""
     if teacher is None:
         teacher = precision == 1
-    kw = dict(batch=B, N=N, T=1.0, quad=hummingbird(), nb=nb, dt_pred=0.01)
+    kw = dict(batch=B, N=N, T=1.0, quad=hummingbird(), nb=nb, dt_pred=0.01, skip=skip)
     if nb:
         kw.update(basis=rgp_basis_linspace(12.0, nb), theta=[1.0, 0.1, 0.1])
     e, o = make_engine(EngineConfig(precision=precision, **kw)), OracleEngine(EngineConfig(**kw))
@@ -270,22 +273,23 @@ def case_swarm_closed_loop(make_engine, B, N, nb, K, precision=0, seed=1, plant_
     return worst
 
 
-def case_saturating_references(make_engine, B=3, K=40, precision=0):
+def case_saturating_references(make_engine, B=3, K=40, precision=0, N=20, nb=10, tune=None, amplitude=1.0):
     """Teacher-forced run on deliberately infeasible references (fast lateral sinusoid + vertical steps): the thrust
     saturates on large parts of the horizon and the working set changes by many inputs per step, so the warm
     active-set attempt goes through many working sets (restarted factorisations, bulk pins / releases) and regularly
     gives up to the interior-point fallback.  Returns (worst relative control deviation over the instance-steps that
-    report success, histogram of pass counts, number of instance-steps reporting a failed solve)."""
-    N, nb = 20, 10
+    report success, histogram of pass counts, number of instance-steps reporting a failed solve).
+    N, nb: the shape (default: the one the references were made for); tune: mpcq_tuning fields of the engine under test; amplitude: factor on
+    the lateral sinusoid and the vertical steps (a short horizon sees less of the references: tests/test_shape_sweep.py)."""
     kw = dict(batch=B, N=N, quad=hummingbird(), nb=nb, basis=rgp_basis_linspace(12.0, nb))
-    e, o = make_engine(EngineConfig(precision=precision, **kw)), OracleEngine(EngineConfig(**kw))
+    e, o = make_engine(EngineConfig(precision=precision, tune=tune, **kw)), OracleEngine(EngineConfig(**kw))
     T = 60 + K * 5
     traj = np.zeros((B, T, 13)); traj[:, :, 3] = 1.0
     t = np.arange(T) * 0.01
     for b in range(B):
-        A, w = 2.0 + b, 3.0 + 0.7 * b
+        A, w = amplitude * (2.0 + b), 3.0 + 0.7 * b
         traj[b, :, 0] = A * np.sin(w * t); traj[b, :, 7] = A * w * np.cos(w * t)
-        traj[b, :, 2] = 3.0 + 1.5 * np.sign(np.sin(2.0 * t + b))
+        traj[b, :, 2] = 3.0 + amplitude * 1.5 * np.sign(np.sin(2.0 * t + b))
     lens = np.full(B, T, dtype=np.int32)
     e.set_trajectories(traj, lens); o.set_trajectories(traj, lens)
     x = np.tile(np.array([0, 0, 3.0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0]), (B, 1))

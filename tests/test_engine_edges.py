@@ -242,9 +242,18 @@ def _free_running_equals_lockstep(lib):
     trajectory lengths so that some instances run past the end of their reference inside the launch."""
     from mpc_quad_ros_amd.trajectories import swarm_trajectories
     big = lib is None
-    B, N, nb, K = (64, 20, 10, 40) if big else (3, 20, 10, 9)
+    # the specialised N = 20 / nb = 10 pair, then any-shape pairs off that grid (tests/test_shape_sweep.py: a single cost-to-go tile, the
+    # first partial second register row) at a batch that is no multiple of the 8-quadrotor granule
+    for B, N, nb, K in ((64, 20, 10, 40) if big else (3, 20, 10, 9), (9, 3, 7, 9), (9, 17, 10, 40) if big else (3, 17, 10, 5)):
+        _free_running_equals_lockstep_shape(lib, B, N, nb, K)
+
+
+def _free_running_equals_lockstep_shape(lib, B, N, nb, K):
+    from mpc_quad_ros_amd.trajectories import swarm_trajectories
     traj, lens = swarm_trajectories(5, 0, B)
     lens = lens.copy(); lens[0] = 6
+    if (N, nb) != (20, 10):
+        lens[B - 1] = 3; lens[B // 2] = K
     x0 = np.tile(np.array([0, 0, 3.0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0]), (B, 1))
     for precision in (0, 1):
         res = []

@@ -349,7 +349,23 @@ def test_config4_full_size():
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
 
 
-@pytest.mark.parametrize("shape", [(20, 10), (20, 20), (50, 50), (10, 10)], ids=["N20nb10", "N20nb20", "N50nb50", "N10nb10-any-shape"])
+# shapes off the grid of the specialised instances (tests/test_shape_sweep.py: a single cost-to-go tile / the first partial second register
+# row / nb > 64), at a batch that is no multiple of the 8-quadrotor granule and with ragged trajectory lengths
+OFF_GRID = [(3, 7), (17, 10), (33, 65)]
+OFF_GRID_IDS = ["N3nb7-any-shape", "N17nb10-any-shape", "N33nb65-any-shape"]
+
+
+def off_grid_batch(pre):
+    """B = 9 quadrotors whose trajectories end at different periods, inside the window that starts `pre` periods in."""
+    from mpc_quad_ros_amd.trajectories import swarm_trajectories
+    traj, lens = swarm_trajectories(13, 0, 9)
+    lens = lens.copy()
+    lens[[0, 2, 5, 7]] = pre + np.array([6, 1, 11, 17])
+    return traj, lens
+
+
+@pytest.mark.parametrize("shape", [(20, 10), (20, 20), (50, 50), (10, 10)] + OFF_GRID,
+                         ids=["N20nb10", "N20nb20", "N50nb50", "N10nb10-any-shape"] + OFF_GRID_IDS)
 @pytest.mark.parametrize("precision", [0, 1])
 @pytest.mark.parametrize("start", ["cold", "in-flight"])
 def test_free_running_equals_lockstep_every_instance(precision, shape, start):
@@ -367,6 +383,9 @@ def test_free_running_equals_lockstep_every_instance(precision, shape, start):
         pre = 0
     traj, lens = swarm_trajectories(13, 0, B)
     lens = lens.copy(); lens[0] = 6                      # one trajectory ends inside the window
+    if shape in OFF_GRID:
+        B = 9
+        traj, lens = off_grid_batch(pre)
     x0 = np.tile(np.array([0, 0, 3.0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0]), (B, 1))
     out = []
     for mode in ("sim_steps", "sim_run"):
@@ -387,7 +406,8 @@ def test_free_running_equals_lockstep_every_instance(precision, shape, start):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("shape", [(20, 10), (20, 20), (50, 50), (10, 10)], ids=["N20nb10", "N20nb20", "N50nb50", "N10nb10-any-shape"])
+@pytest.mark.parametrize("shape", [(20, 10), (20, 20), (50, 50), (10, 10)] + OFF_GRID,
+                         ids=["N20nb10", "N20nb20", "N50nb50", "N10nb10-any-shape"] + OFF_GRID_IDS)
 def test_compact_layout_free_running_equals_lockstep(shape):
     """The compact layout (large batches: six quadrotors per CU instead of four in fp64 at N = 20) as lockstep launches of the
     shape-specialised instance and as one persistent launch of the any-shape instance, 150 periods into the flights: bit for
@@ -399,6 +419,9 @@ def test_compact_layout_free_running_equals_lockstep(shape):
     B, pre, K = (256, 150, 24) if N <= 20 else (64, 40, 12)
     traj, lens = swarm_trajectories(13, 0, B)
     lens = lens.copy(); lens[0] = pre + 6                # one trajectory ends inside the window
+    if shape in OFF_GRID:
+        B = 9
+        traj, lens = off_grid_batch(pre)
     x0 = np.tile(np.array([0, 0, 3.0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0]), (B, 1))
     out = []
     for mode, tune in (("sim_steps", dict(stage_mem="compact")), ("sim_run", dict(stage_mem="compact")), ("sim_steps", None)):
