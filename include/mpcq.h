@@ -152,7 +152,8 @@ const char* mpcq_last_error(void);
  * read-out (csrc/mpcq_predict.hpp), since 0.6.5 the device missions (csrc/mpcq_mission.hpp), since 0.6.6 the device circle generator
  * (csrc/mpcq_circle.hpp), since 0.6.7 the flight scoreboard (csrc/mpcq_score.hpp) and, with mpcq_rgp_train / mpcq_record_train, the device
  * trainer (csrc/mpcq_train.hpp with csrc/mpcq_learn_core.hpp, which mpcq_learn.hip shares).  The number stays 0.6.7 with the trainer:
- * tests/test_score.py pins it; the eight digits tell a library with the trainer from one without. */
+ * tests/test_score.py pins it; the eight digits tell a library with the trainer from one without.  The same holds for the fleet
+ * (mpcq_fleet_*, csrc/mpcq_fleet.hpp), which joined the eight digits after the trainer. */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -589,6 +590,44 @@ int mpcq_rgp_train(mpcq_engine* e, const mpcq_train_spec* spec, const double* v_
  * T = nrows.  MPCQ_ERR_STATE: no active recording (and the rule above).  MPCQ_ERR_INVALID: MPCQ_RECORD_DRAG not recorded, a window
  * outside the rows recorded so far (nrows < 1, or < 2 with pair_next, included), the argument rules of mpcq_rgp_train. */
 int mpcq_record_train(mpcq_engine* e, const mpcq_train_spec* spec, int32_t row0, int32_t nrows, mpcq_train_out* out);
+
+/* ---- the fleet: every quadrotor its own plant.  Without it all B quadrotors of an engine fly the one Quadrotor3D of mpcq_config, in its
+ * drag = True, payload = False corner.  The reference's plant knows more (src/quad.py): a per-rotor rotor_functionality (:86-87, used in
+ * thrust :344 and torques :371), a payload_mass (:93-94, used at :353) and body-frame disturbance force and torque f_d, t_d
+ * (one_step_forward / f_vel / f_rate, :166-190, :348-349, :375-377).  A fleet is a table of B such plants on the device; while one is set,
+ * the plant update of every period is a launch of a kernel that integrates each quadrotor with its own row (csrc/mpcq_fleet.hpp).  The
+ * CONTROLLER keeps the engine's model (mpcq_config): only the plant changes, so the mismatch is what the RGP has to learn -- a sweep over
+ * mass, drag, payload, rotor faults and gusts is one batch, scored per flight (mpcq_score_*).  g stays the engine's.
+ * With f = u * rotor_functionality * max_thrust (u clipped to [0, 1] first, as Quadrotor3D.update does), R the rotation of the attitude:
+ *     dv = R ([0, 0, sum f] + a_drag_body(v) mass + f_d) / mass - [0, 0, g] - [0, 0, payload_mass g / mass]
+ *     dr = (torques of f through y_f, -x_f, z_l_tau + t_d + gyroscopic term) / J
+ * integrated by the reference's RK4 (:181-186), n_sub substeps of sim_dt per period.  f_d / mass, t_d / J, payload_mass g / mass and the
+ * reciprocals of mass and J are formed once, at mpcq_fleet_set.  A row that equals the engine's own plant with payload 0, functionality
+ * 1 and no disturbance gives bit for bit the engine's shared plant: every extra is then an exact * 1.0 or + 0.0. */
+typedef struct mpcq_plant {              /* one quadrotor's Quadrotor3D; g stays the engine's */
+  double mass, J[3], max_thrust, x_f[4], y_f[4], z_l_tau[4];
+  double rotor_drag[3], aero_drag;       /* src/quad.py:79-89 */
+  double payload_mass;                   /* a_payload = -payload_mass g / mass, z only, as src/quad.py:353 has it (its own TODO included) */
+  double rotor_functionality[4];         /* f_thrust = u * functionality * max_thrust, in thrust AND torques (:344, :371); each in [0, 1] */
+  double f_d[3], t_d[3];                 /* body-frame disturbance force [N] and torque [N m] (:348, :375-377) */
+  int32_t d_from, d_to;                  /* f_d, t_d act in fleet periods d_from <= p < d_to; d_to <= d_from: never */
+} mpcq_plant;
+/* The fleet period p counts the plant updates the engine has made since period0 was set: one per control period of mpcq_sim_steps /
+ * mpcq_sim_control_periods (the same p for every group of that period, see mpcq_tuning.groups) and one per mpcq_sim_plant_period.
+ * mpcq_step / mpcq_step_device_async / mpcq_solve update no plant -- the caller owns it -- and are unaffected.  While a fleet is set every
+ * plant update of mpcq_sim_steps is a launch of its own, behind the recorder's row and the score and in front of the mission launch (a
+ * mission plans from the fleet plant's state).  mpcq_sim_run (one persistent launch with the shared plant fused in) flies no fleet:
+ * MPCQ_ERR_STATE while one is set.  mpcq_reset keeps the table and the period, mpcq_destroy frees it.
+ *
+ * mpcq_fleet_set uploads plants [B] (plant_size = the caller's sizeof(mpcq_plant)); calling it again replaces the table.  period0 >= 0
+ * sets the fleet period, -1 keeps it (0 if no fleet is set).  MPCQ_ERR_INVALID, with the engine left as it was and mpcq_last_error()
+ * naming the quadrotor and the field: plants NULL, a plant_size that is not this library's, period0 < -1, a value that is not finite,
+ * mass, J or max_thrust <= 0, a rotor functionality outside [0, 1]. */
+int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants /*[B]*/, uint64_t plant_size, int64_t period0 /*>= 0 sets the fleet period; -1 keeps it (0 if none active)*/);
+/* The table as it was set (exactly: the host's copy) and the fleet period.  MPCQ_ERR_STATE: no fleet set; MPCQ_ERR_INVALID: plant_size. */
+int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants /*[B] or NULL*/, uint64_t plant_size, int64_t* period /*or NULL*/);
+/* back to the engine's shared plant; launches as before this change.  MPCQ_ERR_STATE: no fleet set. */
+int mpcq_fleet_stop(mpcq_engine* e);
 
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)

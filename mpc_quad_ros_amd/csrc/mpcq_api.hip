@@ -29,6 +29,7 @@
 #include "mpcq_score.hpp"
 #include "mpcq_predict.hpp"
 #include "mpcq_train.hpp"
+#include "mpcq_fleet.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -250,6 +251,14 @@ struct Score {
   DevBuf<double> d_table;   // [B,F,16]
   DevBuf<int> d_int;        // cur [B] | used [B] | overflow [B]
 };
+// The fleet (mpcq_fleet_*, mpcq_fleet.hpp): every quadrotor its own plant.  The table as the caller set it (what mpcq_fleet_get returns) and
+// its field-major device form; the launch is EngineT::plant_launch, in the place of the shared plant's.
+struct Fleet {
+  bool on = false;
+  long long period = 0;            // plant updates since period0 was set
+  std::vector<mpcq_plant> plants;  // [B]
+  DevBuf<double> d_tab;            // [fleet::NF][B]
+};
 // Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
 // on a stream of its own, the event that marks the end of its part of a call.
 struct Group {
@@ -303,6 +312,8 @@ struct mpcq_engine : EngineQueues {
   int mission_next_period() { return ms.on ? (int)ms.periods++ : -1; }   // the number of the period about to be issued (-1: no mission)
   Score sc;                      // mpcq_score_start .. mpcq_score_stop
   long long score_next_period() { return sc.on ? sc.periods++ : -1; }     // the same for the scoreboard (-1: no score running)
+  Fleet fl;                      // mpcq_fleet_set .. mpcq_fleet_stop
+  long long fleet_next_period() { return fl.on ? fl.period++ : -1; }       // the fleet period of the plant update about to be issued (-1: no fleet)
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
   std::vector<double> kxinv64;
   struct PredictScratch {
@@ -845,6 +856,18 @@ struct EngineT : mpcq_engine {
     a.Tmax = m.Tmax; a.N = N; a.skip = m.skip;
     hipLaunchKernelGGL(mpcq::score::score_kernel, dim3(mpcq::score::grid((long)n * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, a);
   }
+  // The plant update of the quadrotors [b0, b0 + n): n_sub substeps of sim_dt on xs [B,13] with the controls st.w.  The engine's shared plant
+  // (plant_kernel), or with a fleet set (fper >= 0: its fleet period) every quadrotor's own (fleet_plant_kernel).
+  void plant_launch(hipStream_t s, int b0, int n, double* xs, int n_sub, double sim_dt, long long fper) {
+    if (fper < 0) {
+      hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((n + 63) / 64), dim3(64), 0, s, m, xs + (size_t)b0 * 13, st.w + (size_t)b0 * 4, n_sub, sim_dt, n);
+      return;
+    }
+    mpcq::fleet::Args a;
+    a.tab = fl.d_tab.p; a.B = B; a.b0 = b0; a.n = n; a.g = m.g; a.period = (double)fper;
+    a.xs = xs; a.w = st.w; a.n_sub = n_sub; a.sim_dt = sim_dt;
+    hipLaunchKernelGGL(mpcq::fleet::fleet_plant_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a);
+  }
   // one lockstep period of the quadrotors [b0, b0 + nq) on stream `strm`; ev_begin (if any) is recorded in front of the STEP kernel, behind
   // the ordering launch, so that the event pairs of sim_steps time the step kernel alone
   void launch_period(const mpcq::DevState<T>& s, int mode, hipEvent_t ev_begin, hipStream_t strm, int b0, int nq) {
@@ -862,8 +885,10 @@ struct EngineT : mpcq_engine {
   // (sper >= 0: a score is running and this is its period number) -> the plant kernel
   // (plant: s.run_nsub substeps of s.run_dt on s.run_x) -> the mission launch (mper >= 0: a mission is active and this is its period
   // number; the flights start at the plant state behind its update, or without a plant at the period's measurement).  Every event is
-  // optional.  The caller asks hipGetLastError once it has issued all it has to issue.
-  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, long long sper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant) {
+  // optional.  The caller asks hipGetLastError once it has issued all it has to issue.  fper >= 0: a fleet is set and this is the fleet
+  // period of the plant update, which is then the fleet's launch (plant_launch).
+  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, long long sper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant,
+             long long fper = -1) {
     const Group& g = groups[gi];
     if (g.n <= 0) return 0;
     if (row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
@@ -872,8 +897,7 @@ struct EngineT : mpcq_engine {
     if (ev_end) HIP_TRY(hipEventRecord(ev_end, g.stream));
     if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
     if (sper >= 0) score_write(g.stream, g.b0, g.n, sper, s.x_meas);
-    if (plant)
-      hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((g.n + 63) / 64), dim3(64), 0, g.stream, m, s.run_x + (size_t)g.b0 * 13, st.w + (size_t)g.b0 * 4, s.run_nsub, s.run_dt, g.n);
+    if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, fper);
     if (mper >= 0) mission_launch(this, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, mper);
     return 0;
   }
@@ -986,8 +1010,8 @@ struct EngineT : mpcq_engine {
     // it overlaps that launch's global loads; only the update after the last period needs the plant kernel.  Streaming batches
     // (split_plant, see create): every update is a launch of the plant kernel.  Same arithmetic, same results either way.
     // An active mission plans from the plant state behind the period's update, so it needs that update in front of its launch: every
-    // update is a launch then, too.
-    const bool split = split_plant || ms.on;
+    // update is a launch then, too.  A fleet's plants are integrated by a kernel of their own (mpcq_fleet.hpp): every update is its launch.
+    const bool split = split_plant || ms.on || fl.on;
     s2.run_x = d_xs; s2.run_steps = 1; s2.run_nsub = n_sub; s2.run_dt = sim_dt;
     // Groups (see init): the K periods {order, step, plant} of a group go to its stream, issued period by period round the groups so that
     // the host feeds every queue.  The group streams start behind everything issued on the engine's stream and the engine's stream
@@ -1001,10 +1025,11 @@ struct EngineT : mpcq_engine {
       const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of a group cover the selection inside it)
       const int mper = mission_next_period();
       const long long sper = score_next_period();
+      const long long fper = fleet_next_period();   // (one fleet period per control period: the same for every group)
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
       for (int g = 0; g < G; ++g) {
         hipEvent_t* pair = g == 0 && k % stride == 0 ? &kev[2 * (k / stride)] : nullptr;
-        if ((rc = period(g, s2, mode, row, mper, sper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1))) return rc;
+        if ((rc = period(g, s2, mode, row, mper, sper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1, fper))) return rc;
       }
     }
     for (int g = 1; g < G; ++g) {
@@ -1031,6 +1056,7 @@ struct EngineT : mpcq_engine {
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
     if (sc.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot score flights (one persistent launch): mpcq_score_stop first, or use mpcq_sim_steps");
+    if (fl.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a fleet (one persistent launch): mpcq_fleet_stop first, or use mpcq_sim_steps");
     if (K <= 0) return 0;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
@@ -1091,7 +1117,7 @@ struct EngineT : mpcq_engine {
   int sim_plant(const double* w, int n_sub, double sim_dt) override {
     int rc;
     if (w && (rc = h2d(st.w, w, (size_t)B * 4))) return rc;
-    hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, stream, m, d_xs, st.w, n_sub, sim_dt, B);
+    plant_launch(stream, 0, B, d_xs, n_sub, sim_dt, fleet_next_period());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
@@ -1801,6 +1827,73 @@ int mpcq_score_stop(mpcq_engine* e) {
   if (!e->sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_stop: no score running");
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the table)
   e->sc = Score();
+  return 0;
+}
+
+// ---- the fleet (mpcq_fleet.hpp; the launch: EngineT::plant_launch, in the place of the shared plant's launch of a period)
+int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants, uint64_t plant_size, int64_t period0) {
+  ENTER(e);
+  namespace ft = mpcq::fleet;
+  if (!plants) return fail(MPCQ_ERR_INVALID, "mpcq_fleet_set: plants is NULL");
+  if (plant_size != sizeof(mpcq_plant))
+    return fail(MPCQ_ERR_INVALID, "mpcq_fleet_set: plant_size " + std::to_string(plant_size) + " is not this library's sizeof(mpcq_plant) = " + std::to_string(sizeof(mpcq_plant)));
+  if (period0 < -1) return fail(MPCQ_ERR_INVALID, "mpcq_fleet_set: period0 must be >= 0, or -1 to keep the fleet period");
+  const size_t B = e->B;
+  // every rule is checked before anything of the engine changes
+  for (size_t b = 0; b < B; ++b) {
+    const mpcq_plant& p = plants[b];
+    auto bad = [&](const char* field, int i, const char* rule) {
+      return fail(MPCQ_ERR_INVALID, "mpcq_fleet_set: quadrotor " + std::to_string(b) + ": " + field + (i >= 0 ? "[" + std::to_string(i) + "]" : std::string()) + " " + rule);
+    };
+    struct Field { const char* name; const double* v; int n; int rule; };   // rule 1: > 0; 2: in [0, 1]
+    const Field fields[] = {{"mass", &p.mass, 1, 1}, {"J", p.J, 3, 1}, {"max_thrust", &p.max_thrust, 1, 1}, {"x_f", p.x_f, 4, 0}, {"y_f", p.y_f, 4, 0},
+                            {"z_l_tau", p.z_l_tau, 4, 0}, {"rotor_drag", p.rotor_drag, 3, 0}, {"aero_drag", &p.aero_drag, 1, 0},
+                            {"payload_mass", &p.payload_mass, 1, 0}, {"rotor_functionality", p.rotor_functionality, 4, 2}, {"f_d", p.f_d, 3, 0},
+                            {"t_d", p.t_d, 3, 0}};
+    for (const Field& f : fields)
+      for (int i = 0; i < f.n; ++i) {
+        const int at = f.n > 1 ? i : -1;
+        if (!std::isfinite(f.v[i])) return bad(f.name, at, "is not finite");
+        if (f.rule == 1 && !(f.v[i] > 0)) return bad(f.name, at, "must be > 0");
+        if (f.rule == 2 && !(f.v[i] >= 0 && f.v[i] <= 1)) return bad(f.name, at, "must be in [0, 1]");
+      }
+  }
+  std::vector<double> tab((size_t)ft::NF * B), row(ft::NF);
+  for (size_t b = 0; b < B; ++b) {
+    ft::pack(plants[b], e->cfg.g, row.data());
+    for (int f = 0; f < ft::NF; ++f) tab[(size_t)f * B + b] = row[f];
+  }
+  Fleet& fl = e->fl;
+  // The new table goes to a buffer of its own and takes the old one's place only once it is complete on the device: a failed allocation
+  // or copy leaves the engine flying the table it had.
+  DevBuf<double> fresh;
+  if (fresh.grow(tab.size()) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MPCQ_ERR_DEVICE, "mpcq_fleet_set: cannot allocate " + std::to_string(tab.size() * sizeof(double)) + " bytes");
+  }
+  HIP_TRY(hipMemcpyAsync(fresh.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (behind it nothing the engine has enqueued reads the table that is replaced: the calls that launch the plant return synchronised)
+  fl.d_tab = std::move(fresh);
+  fl.plants.assign(plants, plants + B);
+  if (period0 >= 0) fl.period = period0;
+  else if (!fl.on) fl.period = 0;
+  fl.on = true;
+  return 0;
+}
+int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants, uint64_t plant_size, int64_t* period) {
+  ENTER(e);
+  const Fleet& fl = e->fl;
+  if (!fl.on) return fail(MPCQ_ERR_STATE, "mpcq_fleet_get: no fleet set");
+  if (plant_size != sizeof(mpcq_plant)) return fail(MPCQ_ERR_INVALID, "mpcq_fleet_get: plant_size is not this library's sizeof(mpcq_plant)");
+  if (plants) std::memcpy(plants, fl.plants.data(), fl.plants.size() * sizeof(mpcq_plant));
+  if (period) *period = fl.period;
+  return 0;
+}
+int mpcq_fleet_stop(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->fl.on) return fail(MPCQ_ERR_STATE, "mpcq_fleet_stop: no fleet set");
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->fl = Fleet();
   return 0;
 }
 

@@ -374,6 +374,34 @@ class Engine:
             out[name] = np.where(found, v, -1 if v.dtype.kind == "i" else np.nan)
         return out
 
+    # ---- the fleet: every quadrotor its own plant (the controller keeps the engine's model)
+    def fleet_set(self, plants, period0=0):
+        """Fly plants [B] of params.PLANT_DTYPE (params.fleet_defaults / fleet_sample build them) in every plant update from now on:
+        sim_steps, sim_control_periods, sim_plant_period.  period0 >= 0 sets the fleet period, which the disturbance windows
+        [d_from, d_to) refer to and every plant update advances by one; -1 keeps it.  Calling it again replaces the table."""
+        from .params import PLANT_DTYPE
+        plants = np.ascontiguousarray(plants)
+        if plants.dtype != PLANT_DTYPE or plants.shape != (self.B,):
+            raise ValueError(f"plants must be a [B={self.B}] array of params.PLANT_DTYPE")
+        self._check(self.lib.mpcq_fleet_set(self.h, plants.ctypes.data_as(ctypes.c_void_p), PLANT_DTYPE.itemsize, int(period0)))
+
+    def fleet_get(self):
+        """(plants [B] as they were set, the fleet period)."""
+        from .params import PLANT_DTYPE
+        plants, period = np.zeros(self.B, PLANT_DTYPE), ctypes.c_int64()
+        self._check(self.lib.mpcq_fleet_get(self.h, plants.ctypes.data_as(ctypes.c_void_p), PLANT_DTYPE.itemsize, ctypes.byref(period)))
+        return plants, period.value
+
+    def fleet_stop(self):
+        """Back to the engine's shared plant."""
+        self._check(self.lib.mpcq_fleet_stop(self.h))
+
+    def fleet_drag_truth(self, v):
+        """The body-frame drag acceleration [B, 3, M] of every plant of the fleet at body velocities v ([M], [3, M] or [B, 3, M]), from
+        the table in numpy (params.fleet_drag_accel): the curve rgp_predict is to be compared with."""
+        from .params import fleet_drag_accel
+        return fleet_drag_accel(self.fleet_get()[0], v)
+
     def set_reference(self, yref, yrefN):
         yref = self._f(yref, (self.B, self.N, NY))
         yrefN = self._f(yrefN, (self.B, NX))

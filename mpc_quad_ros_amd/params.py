@@ -194,3 +194,76 @@ def static_gp_theta(theta):
 def rgp_basis_linspace(v_max: float, nb: int) -> np.ndarray:
     """Node basis: np.linspace(-v_max, v_max, nb) on each axis, src/mpc_controller_node.py:212."""
     return np.tile(np.linspace(-v_max, v_max, nb), (3, 1))
+
+
+# ---------------------------------------------------------------------------------------------
+# The fleet (include/mpcq.h mpcq_fleet_*): every quadrotor its own plant -- the reference's whole Quadrotor3D (src/quad.py:36-94), with
+# payload, rotor functionality and body-frame disturbances, while the controller keeps the engine's model.
+PLANT_DTYPE = np.dtype([
+    ("mass", np.float64), ("J", np.float64, (3,)), ("max_thrust", np.float64),
+    ("x_f", np.float64, (4,)), ("y_f", np.float64, (4,)), ("z_l_tau", np.float64, (4,)),
+    ("rotor_drag", np.float64, (3,)), ("aero_drag", np.float64), ("payload_mass", np.float64),
+    ("rotor_functionality", np.float64, (4,)), ("f_d", np.float64, (3,)), ("t_d", np.float64, (3,)),
+    ("d_from", np.int32), ("d_to", np.int32)], align=True)
+"""Binary layout of ``mpcq_plant`` (include/mpcq.h)."""
+
+
+def fleet_defaults(cfg: "EngineConfig | QuadParams", count: int) -> np.ndarray:
+    """`count` plants that restate the engine's own (cfg: an EngineConfig or its QuadParams): payload 0, every rotor functional, no
+    disturbance.  Flying them is bit for bit flying without a fleet; the start of every hand-made table."""
+    q = cfg.quad if isinstance(cfg, EngineConfig) else cfg
+    p = np.zeros(count, PLANT_DTYPE)
+    p["mass"], p["max_thrust"], p["aero_drag"] = q.mass, q.max_thrust, q.aero_drag
+    for name in ("J", "x_f", "y_f", "z_l_tau", "rotor_drag"):
+        p[name] = np.asarray(getattr(q, name), dtype=np.float64)
+    p["rotor_functionality"] = 1.0
+    return p
+
+
+def fleet_sample(seed: int, first_index: int, count: int, cfg: "EngineConfig | QuadParams", spread: float = 1.3, payload_max: float = 0.0,
+                 fault_prob: float = 0.0, fault_min: float = 0.5, gust_force: float = 0.0, gust_torque: float = 0.0, gust_window=(0, 0)) -> np.ndarray:
+    """A randomised fleet around the engine's plant, quadrotors first_index .. first_index + count - 1 of it.  Every quadrotor is drawn
+    from a generator of its own, seeded with (seed, global index), so shards of a swarm agree with the whole (as swarm_trajectories).
+      spread       mass, each J, max_thrust, each rotor drag and the aero drag are multiplied by independent factors, log-uniform in
+                   [1 / spread, spread] (1: unchanged); a float, or a dict by field name ('mass', 'J', 'max_thrust', 'rotor_drag', 'aero_drag')
+      payload_max  payload_mass uniform in [0, payload_max] kg
+      fault_prob   with this probability ONE rotor of the quadrotor, picked uniformly, has functionality uniform in [fault_min, 1]
+      gust_force, gust_torque   standard deviations [N], [N m] of the normal body-frame f_d, t_d, which act in the fleet periods
+                   gust_window = (d_from, d_to)"""
+    p = fleet_defaults(cfg, count)
+    sp = spread if isinstance(spread, dict) else {k: spread for k in ("mass", "J", "max_thrust", "rotor_drag", "aero_drag")}
+    unknown = set(sp) - {"mass", "J", "max_thrust", "rotor_drag", "aero_drag"}
+    if unknown or any(not v >= 1.0 for v in sp.values()):
+        raise ValueError("spread: factors >= 1 for mass, J, max_thrust, rotor_drag, aero_drag")
+    if not 0.0 <= fault_prob <= 1.0 or not 0.0 <= fault_min <= 1.0 or payload_max < 0:
+        raise ValueError("fault_prob and fault_min in [0, 1], payload_max >= 0")
+    for i in range(count):
+        rng = np.random.default_rng([int(seed), int(first_index) + i])
+        # (every draw is made whatever the options, so that one option does not move the others' values)
+        f = {k: np.exp(rng.uniform(-1.0, 1.0, n)) for k, n in (("mass", 1), ("J", 3), ("max_thrust", 1), ("rotor_drag", 3), ("aero_drag", 1))}
+        pay, hit, rotor, level = rng.uniform(), rng.uniform(), rng.integers(4), rng.uniform()
+        fd, td = rng.normal(size=3), rng.normal(size=3)
+        for k, v in f.items():
+            fac = v ** np.log(sp.get(k, 1.0))
+            p[k][i] = p[k][i] * (fac if fac.size > 1 else fac[0])
+        p["payload_mass"][i] = pay * payload_max
+        if hit < fault_prob:
+            p["rotor_functionality"][i, rotor] = fault_min + (1.0 - fault_min) * level
+        p["f_d"][i], p["t_d"][i] = gust_force * fd + 0.0, gust_torque * td + 0.0   # (+ 0.0: no -0.0 where there is no gust)
+    p["d_from"], p["d_to"] = int(gust_window[0]), int(gust_window[1])
+    return p
+
+
+def fleet_drag_accel(plants: np.ndarray, v) -> np.ndarray:
+    """Body-frame drag acceleration of every plant at body velocities v, Quadrotor3D.get_aero_drag(body_frame=True) (src/quad.py:256-277):
+    -aero_drag v^2 sign(v) / mass - rotor_drag v / mass.  v [M] (one grid for all axes), [3, M] or [B, 3, M] -> [B, 3, M]."""
+    plants = np.asarray(plants)
+    v = np.asarray(v, dtype=np.float64)
+    B = plants.shape[0]
+    if v.ndim == 1:
+        v = np.tile(v, (3, 1))
+    v = np.broadcast_to(v, (B,) + v.shape[-2:])
+    mass = plants["mass"][:, None, None]
+    a = -plants["aero_drag"][:, None, None] * v ** 2 * np.sign(v) / mass
+    a -= plants["rotor_drag"][:, :, None] * v / mass
+    return a
