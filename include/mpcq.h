@@ -153,7 +153,8 @@ const char* mpcq_last_error(void);
  * (csrc/mpcq_circle.hpp), since 0.6.7 the flight scoreboard (csrc/mpcq_score.hpp) and, with mpcq_rgp_train / mpcq_record_train, the device
  * trainer (csrc/mpcq_train.hpp with csrc/mpcq_learn_core.hpp, which mpcq_learn.hip shares).  The number stays 0.6.7 with the trainer:
  * tests/test_score.py pins it; the eight digits tell a library with the trainer from one without.  The same holds for the fleet
- * (mpcq_fleet_*, csrc/mpcq_fleet.hpp), which joined the eight digits after the trainer. */
+ * (mpcq_fleet_*, csrc/mpcq_fleet.hpp), which joined the eight digits after the trainer, and for the exploration (mpcq_explore_*,
+ * csrc/mpcq_explore.hpp), which joined them after the fleet. */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -628,6 +629,47 @@ int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants /*[B]*/, uint64_t pl
 int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants /*[B] or NULL*/, uint64_t plant_size, int64_t* period /*or NULL*/);
 /* back to the engine's shared plant; launches as before this change.  MPCQ_ERR_STATE: no fleet set. */
 int mpcq_fleet_stop(mpcq_engine* e);
+
+/* ---- exploration: mission limits from each quadrotor's envelope.  The reference's exploration loop (src/explore_trajectories.py:59-125)
+ * flies one flight, trains a GP on that run and asks Explorer (src/Explorer.py:23-84) how far the training inputs reach in body-frame
+ * velocity; the next flight gets v_max = a_max = velocity_to_explore, each clipped at 30 (:67-78).  Here the RGP regresses every period,
+ * so the samples a flight contributed are the v_body of its periods, and the rule runs on the device, per quadrotor, in the period a
+ * flight ends: no host decides how fast the next leg of a mission is flown.
+ *   Envelope.  env [B,3,2] holds min and max of v_body per axis, samples [B] how many periods it covers.  The sample of a period is
+ * v_body = R(q)^T v of the measurement the period's step solved from -- bit for bit the first three entries of MPCQ_RECORD_DRAG.  With
+ * samples == 0 the envelope reads min = max = 0 on every axis (Explorer's `gpe is None`, src/Explorer.py:70-74).
+ *   Rule (one mpcq_explore_rule per quadrotor).  Over the axes of `axes` (bit i: axis i; 7: all three, the reference):
+ * vabs = max(0, max, |min|) with the reference's strict comparisons (calculate_explored_vmax, src/Explorer.py:51-63), explored = the
+ * smallest vabs, v = explored + step if that is < desired, else desired (calculate_velocity_to_explore, :40-48), v_max = min(v, v_limit),
+ * a_max = min(v, a_limit) (src/explore_trajectories.py:67-78).  The reference's numbers: step 10, desired 20, limits 30.
+ *   Policy.  Quadrotor b is due in a period when finished[b] != 0 && leg[b] < L; if leg_mask[b, leg[b]] != 0 the device writes v_max and
+ * a_max of that leg into the mission's legs table before the mission launch of the same period plans it.  Kind and radius stay: a
+ * circle leg flies its radius at the explored speed.  leg_limits [B,L,3] logs (explored, v_max, a_max) of every leg written so; NaN
+ * where none was (not consumed yet, or not explored).
+ *   Launch.  One launch per period and range of quadrotors, behind the step (and the recorder's row and the score), in front of the
+ * plant and mission launches, on every period a mission runs on: mpcq_sim_steps (each group's range on its stream),
+ * mpcq_sim_control_periods, mpcq_step, mpcq_step_device_async.  mpcq_sim_run: MPCQ_ERR_STATE, as for the mission.  With no exploration
+ * started every launch sequence and result is what it was.
+ *   Two deliberate differences from the reference: it takes the range of the 10 GMM-selected training samples of the run, this the range of
+ * all samples of the flight; and the limits follow the sample range, not the RGP's posterior variance. */
+#define MPCQ_EXPLORE_LAST_FLIGHT 0   /* the reference: every run trains a fresh GP -- the envelope restarts in the period whose step used cursor 0 (a new flight, as MPCQ_RECORD_SOLVER shows it) */
+#define MPCQ_EXPLORE_CUMULATIVE  1   /* the envelope never restarts */
+typedef struct mpcq_explore_rule { double step, desired, v_limit, a_limit; int32_t mode, axes; } mpcq_explore_rule;   /* one per quadrotor */
+/* Start (or, while one runs, replace) the exploration of the mission that is set: rules [B] (rule_size = the caller's
+ * sizeof(mpcq_explore_rule)), leg_mask [B,L] (NULL: every leg is explored), and the envelope to start from: env0 [B,3,2] with
+ * samples0 [B] (what mpcq_explore_get returned: a checkpoint), or both NULL for the empty envelope.  leg_limits starts all NaN.
+ * MPCQ_ERR_STATE: no mission set.  MPCQ_ERR_INVALID, with the engine left as it was and mpcq_last_error() naming the quadrotor: rules
+ * NULL, a rule_size that is not this library's, step / desired / v_limit / a_limit not finite and > 0, mode not 0 or 1, axes outside
+ * 1..7, exactly one of env0 / samples0 given, a negative samples0.
+ * mpcq_mission_set, mpcq_mission_set_legs and mpcq_mission_stop end a running exploration: the table it writes into is gone. */
+int mpcq_explore_start(mpcq_engine* e, const mpcq_explore_rule* rules /*[B]*/, uint64_t rule_size, const uint8_t* leg_mask /*[B,L] or NULL: every leg*/,
+                       const double* env0 /*[B,3,2] or NULL*/, const int64_t* samples0 /*[B] or NULL*/);
+/* Envelope, sample counts and the log, behind everything the engine has enqueued; any pointer may be NULL.  MPCQ_ERR_STATE: no
+ * exploration running. */
+int mpcq_explore_get(mpcq_engine* e, double* env /*[B,3,2]*/, int64_t* samples /*[B]*/, double* leg_limits /*[B,L,3]*/);
+/* Exploration off: the mission flies the rest of its legs with the limits the table holds now (what was written stays written), period
+ * launches are what they are without it.  MPCQ_ERR_STATE: no exploration running. */
+int mpcq_explore_stop(mpcq_engine* e);
 
 /* ---- RGP.learn (src/gp/RGP.py:332-505), SURVEY §8 f4: hyper-parameter learning of the recursive GP (unscented
  * transform over eta = (L, sigma_f, sigma_n) + Kalman / smoother updates) for batch x 3 independent (quadrotor, axis)

@@ -147,6 +147,9 @@ SYMBOLS = [
     ("mpcq_fleet_set", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int64]),
     ("mpcq_fleet_get", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _lp]),
     ("mpcq_fleet_stop", ctypes.c_int, [_vp]),
+    ("mpcq_explore_start", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _dp, _lp]),
+    ("mpcq_explore_get", ctypes.c_int, [_vp, _dp, _lp, _dp]),
+    ("mpcq_explore_stop", ctypes.c_int, [_vp]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),
     ("mpcq_learn_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mpcq_learn_destroy", ctypes.c_int, [_vp]),

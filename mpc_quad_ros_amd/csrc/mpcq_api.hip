@@ -26,6 +26,7 @@
 #include "mpcq_replan_nl.hpp"
 #include "mpcq_mission.hpp"
 #include "mpcq_record.hpp"
+#include "mpcq_explore.hpp"
 #include "mpcq_score.hpp"
 #include "mpcq_predict.hpp"
 #include "mpcq_train.hpp"
@@ -259,6 +260,16 @@ struct Fleet {
   std::vector<mpcq_plant> plants;  // [B]
   DevBuf<double> d_tab;            // [fleet::NF][B]
 };
+// Exploration (mpcq_explore_*, mpcq_explore.hpp): the rules, the envelope of every quadrotor and the log of the limits it chose, on the
+// device; the launch is EngineT::explore_write, between the score's launch and the plant's.  On only while a mission is (it writes into
+// the mission's legs table).
+struct Explore {
+  bool on = false;
+  DevBuf<mpcq_explore_rule> d_rules;   // [B]
+  DevBuf<unsigned char> d_mask;        // [B,L]
+  DevBuf<double> d_f64;                // env [B,3,2] | leg_limits [B,L,3]
+  DevBuf<int64_t> d_samples;           // [B]
+};
 // Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
 // on a stream of its own, the event that marks the end of its part of a call.
 struct Group {
@@ -314,6 +325,7 @@ struct mpcq_engine : EngineQueues {
   long long score_next_period() { return sc.on ? sc.periods++ : -1; }     // the same for the scoreboard (-1: no score running)
   Fleet fl;                      // mpcq_fleet_set .. mpcq_fleet_stop
   long long fleet_next_period() { return fl.on ? fl.period++ : -1; }       // the fleet period of the plant update about to be issued (-1: no fleet)
+  Explore ex;                    // mpcq_explore_start .. mpcq_explore_stop (or the end of the mission)
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
   std::vector<double> kxinv64;
   struct PredictScratch {
@@ -856,6 +868,17 @@ struct EngineT : mpcq_engine {
     a.Tmax = m.Tmax; a.N = N; a.skip = m.skip;
     hipLaunchKernelGGL(mpcq::score::score_kernel, dim3(mpcq::score::grid((long)n * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, a);
   }
+  // behind the score's launch, in front of the plant and mission launches: the period's sample into the envelopes of the quadrotors
+  // [b0, b0 + n) and the limits of the legs the mission launch of this period is about to plan (mpcq_explore.hpp)
+  void explore_write(hipStream_t s, int b0, int n, const double* xmeas) {
+    mpcq::explore::Args a;
+    a.env = ex.d_f64.p; a.leg_limits = a.env + (size_t)B * 6; a.samples = ex.d_samples.p;
+    a.rules = ex.d_rules.p; a.leg_mask = ex.d_mask.p;
+    a.legs = ms.d_legs.p; a.leg = ms.d_int.p; a.L = ms.L;
+    a.idx = st.idx; a.finished = st.finished; a.xmeas = xmeas;
+    a.b0 = b0; a.n = n;
+    hipLaunchKernelGGL(mpcq::explore::explore_kernel, dim3(mpcq::explore::grid(n)), dim3(mpcq::explore::BLOCK), 0, s, a);
+  }
   // The plant update of the quadrotors [b0, b0 + n): n_sub substeps of sim_dt on xs [B,13] with the controls st.w.  The engine's shared plant
   // (plant_kernel), or with a fleet set (fper >= 0: its fleet period) every quadrotor's own (fleet_plant_kernel).
   void plant_launch(hipStream_t s, int b0, int n, double* xs, int n_sub, double sim_dt, long long fper) {
@@ -882,7 +905,7 @@ struct EngineT : mpcq_engine {
   }
   // One period of groups[gi], the only place that issues one.  On the group's stream, in this order: the recorder's snapshot (row >= 0:
   // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the scoreboard's launch
-  // (sper >= 0: a score is running and this is its period number) -> the plant kernel
+  // (sper >= 0: a score is running and this is its period number) -> the exploration launch (an exploration runs and mper >= 0) -> the plant kernel
   // (plant: s.run_nsub substeps of s.run_dt on s.run_x) -> the mission launch (mper >= 0: a mission is active and this is its period
   // number; the flights start at the plant state behind its update, or without a plant at the period's measurement).  Every event is
   // optional.  The caller asks hipGetLastError once it has issued all it has to issue.  fper >= 0: a fleet is set and this is the fleet
@@ -897,6 +920,7 @@ struct EngineT : mpcq_engine {
     if (ev_end) HIP_TRY(hipEventRecord(ev_end, g.stream));
     if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
     if (sper >= 0) score_write(g.stream, g.b0, g.n, sper, s.x_meas);
+    if (ex.on && mper >= 0) explore_write(g.stream, g.b0, g.n, s.x_meas);
     if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, fper);
     if (mper >= 0) mission_launch(this, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, mper);
     return 0;
@@ -1054,6 +1078,7 @@ struct EngineT : mpcq_engine {
   int sim_run(int K, int n_sub, double sim_dt) override {
     if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_run needs mpcq_set_trajectories first");
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
+    if (ex.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot explore (one persistent launch): mpcq_explore_stop and mpcq_mission_stop first, or use mpcq_sim_steps");
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
     if (sc.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot score flights (one persistent launch): mpcq_score_stop first, or use mpcq_sim_steps");
     if (fl.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a fleet (one persistent launch): mpcq_fleet_stop first, or use mpcq_sim_steps");
@@ -1558,6 +1583,7 @@ int mission_begin(const std::string& who, mpcq_engine* e, const mpcq_leg* legs, 
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still read the queue that is replaced)
   Mission& ms = e->ms;
   ms.on = false;
+  e->ex = Explore();   // (an exploration wrote into the table that is replaced)
   if (wp) HIP_TRY(ms.d_wp.grow(nl * n_wp * 3));
   else ms.d_wp.release();
   HIP_TRY(ms.d_legs.grow(nl));
@@ -1647,6 +1673,73 @@ int mpcq_mission_stop(mpcq_engine* e) {
   if (!e->ms.on) return fail(MPCQ_ERR_STATE, "mpcq_mission_stop: no mission set");
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the queue)
   e->ms = Mission();
+  e->ex = Explore();   // (the table an exploration wrote into is gone)
+  return 0;
+}
+
+// ---- exploration (mpcq_explore.hpp; the launch: EngineT::explore_write, behind the score's launch of EngineT::period)
+int mpcq_explore_start(mpcq_engine* e, const mpcq_explore_rule* rules, uint64_t rule_size, const uint8_t* leg_mask, const double* env0, const int64_t* samples0) {
+  ENTER(e);
+  const std::string who("mpcq_explore_start");
+  if (!e->ms.on) return fail(MPCQ_ERR_STATE, who + ": no mission set (the limits go into its legs table)");
+  if (!rules) return fail(MPCQ_ERR_INVALID, who + ": rules is NULL");
+  if (rule_size != sizeof(mpcq_explore_rule))
+    return fail(MPCQ_ERR_INVALID, who + ": rule_size " + std::to_string(rule_size) + " is not this library's sizeof(mpcq_explore_rule) = " + std::to_string(sizeof(mpcq_explore_rule)));
+  if (!env0 != !samples0) return fail(MPCQ_ERR_INVALID, who + ": env0 and samples0 come together (a checkpoint), or both NULL");
+  const size_t B = e->B, nl = B * (size_t)e->ms.L;
+  // every rule is checked before anything of the engine changes
+  for (size_t b = 0; b < B; ++b) {
+    const mpcq_explore_rule& r = rules[b];
+    auto bad = [&](const char* field, const char* rule) { return fail(MPCQ_ERR_INVALID, who + ": quadrotor " + std::to_string(b) + ": " + field + " " + rule); };
+    const struct { const char* name; double v; } fields[] = {{"step", r.step}, {"desired", r.desired}, {"v_limit", r.v_limit}, {"a_limit", r.a_limit}};
+    for (const auto& f : fields)
+      if (!(std::isfinite(f.v) && f.v > 0)) return bad(f.name, "must be finite and > 0");
+    if (r.mode != MPCQ_EXPLORE_LAST_FLIGHT && r.mode != MPCQ_EXPLORE_CUMULATIVE) return bad("mode", "must be 0 (last flight) or 1 (cumulative)");
+    if (r.axes < 1 || r.axes > 7) return bad("axes", "must be in 1..7");
+    if (samples0 && samples0[b] < 0) return bad("samples0", "must be >= 0");
+  }
+  // The new state goes to buffers of its own and takes the old one's place only once it is complete on the device: a failed allocation or
+  // copy leaves the engine exploring as it did (or not at all).
+  Explore fresh;
+  if (fresh.d_rules.grow(B) != hipSuccess || fresh.d_mask.grow(nl) != hipSuccess || fresh.d_f64.grow(B * 6 + nl * 3) != hipSuccess ||
+      fresh.d_samples.grow(B) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MPCQ_ERR_DEVICE, who + ": cannot allocate the rules, the envelopes and the log");
+  }
+  std::vector<double> f64(B * 6 + nl * 3, std::nan(""));   // env | leg_limits (NaN: not written)
+  std::vector<int64_t> smp(B, 0);
+  for (size_t b = 0; b < B; ++b) {
+    const bool have = samples0 && samples0[b] > 0;   // (samples == 0 reads as min = max = 0)
+    for (int k = 0; k < 6; ++k) f64[b * 6 + k] = have ? env0[b * 6 + k] : 0.0;
+    if (have) smp[b] = samples0[b];
+  }
+  const std::vector<unsigned char> all(leg_mask ? 0 : nl, 1);
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the state that is replaced)
+  HIP_TRY(hipMemcpyAsync(fresh.d_rules.p, rules, B * sizeof(mpcq_explore_rule), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(fresh.d_mask.p, leg_mask ? leg_mask : all.data(), nl, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(fresh.d_f64.p, f64.data(), f64.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(fresh.d_samples.p, smp.data(), B * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->ex = std::move(fresh);
+  e->ex.on = true;
+  return 0;
+}
+int mpcq_explore_get(mpcq_engine* e, double* env, int64_t* samples, double* leg_limits) {
+  ENTER(e);
+  const Explore& ex = e->ex;
+  if (!ex.on) return fail(MPCQ_ERR_STATE, "mpcq_explore_get: no exploration running");
+  const size_t B = e->B, nl = B * (size_t)e->ms.L;
+  if (env) HIP_TRY(hipMemcpyAsync(env, ex.d_f64.p, B * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (leg_limits) HIP_TRY(hipMemcpyAsync(leg_limits, ex.d_f64.p + B * 6, nl * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (samples) HIP_TRY(hipMemcpyAsync(samples, ex.d_samples.p, B * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+int mpcq_explore_stop(mpcq_engine* e) {
+  ENTER(e);
+  if (!e->ex.on) return fail(MPCQ_ERR_STATE, "mpcq_explore_stop: no exploration running");
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the envelopes)
+  e->ex = Explore();
   return 0;
 }
 

@@ -28,6 +28,21 @@ __host__ __device__ inline int width(int f, int nb) {
   }
 }
 
+// Component i of v_body = R(q)^T v of the state x [13] (rotmat's R, column i).  The one place the recorder's v_body is computed, and
+// the exploration's sample with it (mpcq_explore.hpp): the envelope of an exploration is bit for bit the minimum and maximum of the
+// recorded rows only if both kernels round alike, and left to itself the compiler fuses these products and sums into multiply-adds
+// differently from kernel to kernel (and, inside record_kernel, from component to component).  So contraction is off here: every
+// operation is rounded on its own, whatever the code around the call.
+__device__ inline double v_body_axis(const double* x, int i) {
+#pragma clang fp contract(off)
+  const double qw = x[3], qx = x[4], qy = x[5], qz = x[6];
+  double r0, r1, r2;   // R[i], R[3 + i], R[6 + i]
+  if (i == 0) { r0 = 1 - 2 * (qy * qy + qz * qz); r1 = 2 * (qx * qy + qw * qz); r2 = 2 * (qx * qz - qw * qy); }
+  else if (i == 1) { r0 = 2 * (qx * qy - qw * qz); r1 = 1 - 2 * (qx * qx + qz * qz); r2 = 2 * (qy * qz + qw * qx); }
+  else { r0 = 2 * (qx * qz + qw * qy); r1 = 2 * (qy * qz - qw * qx); r2 = 1 - 2 * (qx * qx + qy * qy); }
+  return r0 * x[7] + r1 * x[8] + r2 * x[9];
+}
+
 template <typename TQ>
 struct Args {
   const int* sel;      // selection, sorted [count]
@@ -81,17 +96,8 @@ __global__ void __launch_bounds__(64) record_kernel(const Args<TQ> a) {
       const bool hp = sn[NX] != 0.0;
 #pragma unroll
       for (int k = 0; k < NX; ++k) { x[k] = a.xmeas[(size_t)b * NX + k]; xq[k] = hp ? sn[k] : x[k]; }
-      double R[9], Rq[9];
-      rotmat(x + 3, R);
-      rotmat(xq + 3, Rq);
       const int c = e < 3 ? e : e - 3;
-      double vb = 0, vp = 0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (i == c) {
-          vb = R[i] * x[7] + R[3 + i] * x[8] + R[6 + i] * x[9];
-          vp = Rq[i] * xq[7] + Rq[3 + i] * xq[8] + Rq[6 + i] * xq[9];
-        }
+      const double vb = v_body_axis(x, c), vp = v_body_axis(xq, c);
       a.out[F_DRAG][o] = e < 3 ? vb : (vb - vp) / a.dt_pred;
       break;
     }

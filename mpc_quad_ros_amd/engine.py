@@ -402,6 +402,41 @@ class Engine:
         from .params import fleet_drag_accel
         return fleet_drag_accel(self.fleet_get()[0], v)
 
+    # ---- exploration: the limits of the next mission leg from the envelope of body velocities the quadrotor has flown
+    def explore_start(self, rules, leg_mask=None, env=None, samples=None):
+        """Explore with the mission that is set (mpcq_explore_start): in the period a flight ends, v_max and a_max of the quadrotor's
+        next leg are set on the device from its envelope by its rule (params.explore_velocity is the host form).  rules [B] of
+        params.EXPLORE_RULE_DTYPE (params.explore_rules builds them); leg_mask [B, L] (None: every leg is explored); env [B, 3, 2] with
+        samples [B]: the envelope to start from (a checkpoint's explore_get), None for the empty one.  Calling it again replaces rules,
+        mask and envelope and empties the log; mission_set* and mission_stop end the exploration."""
+        from .params import EXPLORE_RULE_DTYPE
+        L = getattr(self, "_mission_legs", None)
+        if L is None:
+            raise _lib.MpcqError("explore_start needs mission_set first")
+        rules = np.ascontiguousarray(rules)
+        if rules.dtype != EXPLORE_RULE_DTYPE or rules.shape != (self.B,):
+            raise ValueError(f"rules must be a [B={self.B}] array of params.EXPLORE_RULE_DTYPE")
+        if leg_mask is not None:
+            leg_mask = np.ascontiguousarray(np.asarray(leg_mask) != 0, dtype=np.uint8)
+            if leg_mask.shape != (self.B, L):
+                raise ValueError(f"leg_mask must be [B={self.B}, L={L}]")
+        env = self._f(env, (self.B, 3, 2))
+        samples = None if samples is None else np.ascontiguousarray(samples, dtype=np.int64).reshape(self.B)
+        self._check(self.lib.mpcq_explore_start(self.h, rules.ctypes.data_as(ctypes.c_void_p), EXPLORE_RULE_DTYPE.itemsize,
+                                                None if leg_mask is None else leg_mask.ctypes.data_as(ctypes.c_void_p), _lib.d(env), _lib.l(samples)))
+
+    def explore_get(self):
+        """dict(env [B, 3, 2]: min and max of v_body per axis (zeros while samples == 0), samples [B], leg_limits [B, L, 3]: (explored,
+        v_max, a_max) of every leg the exploration has set, NaN elsewhere)."""
+        L = getattr(self, "_mission_legs", None) or 0
+        out = dict(env=np.zeros((self.B, 3, 2)), samples=np.zeros(self.B, np.int64), leg_limits=np.zeros((self.B, L, 3)))
+        self._check(self.lib.mpcq_explore_get(self.h, _lib.d(out["env"]), _lib.l(out["samples"]), _lib.d(out["leg_limits"])))
+        return out
+
+    def explore_stop(self):
+        """Exploration off; the mission flies on with the limits its table holds now."""
+        self._check(self.lib.mpcq_explore_stop(self.h))
+
     def set_reference(self, yref, yrefN):
         yref = self._f(yref, (self.B, self.N, NY))
         yrefN = self._f(yrefN, (self.B, NX))

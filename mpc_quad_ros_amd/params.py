@@ -267,3 +267,38 @@ def fleet_drag_accel(plants: np.ndarray, v) -> np.ndarray:
     a = -plants["aero_drag"][:, None, None] * v ** 2 * np.sign(v) / mass
     a -= plants["rotor_drag"][:, :, None] * v / mass
     return a
+
+
+# ---------------------------------------------------------------------------------------------
+# Exploration (include/mpcq.h mpcq_explore_*): the limits of the next mission leg from the envelope of body velocities a quadrotor has
+# flown -- the reference's Explorer (src/Explorer.py:40-84) as src/explore_trajectories.py:59-125 applies it, per quadrotor on the device.
+EXPLORE_LAST_FLIGHT, EXPLORE_CUMULATIVE = 0, 1
+EXPLORE_RULE_DTYPE = np.dtype([("step", np.float64), ("desired", np.float64), ("v_limit", np.float64), ("a_limit", np.float64),
+                               ("mode", np.int32), ("axes", np.int32)], align=True)
+"""Binary layout of ``mpcq_explore_rule`` (include/mpcq.h)."""
+
+
+def explore_rules(B: int, step=10.0, desired=20.0, v_limit=30.0, a_limit=30.0, mode=EXPLORE_LAST_FLIGHT, axes=7) -> np.ndarray:
+    """B rules for Engine.explore_start; every argument a scalar or [B].  The defaults are the reference's numbers: exploration_step 10,
+    desired_explored_vmax 20 (src/Explorer.py:26-27), v_max_limit = a_max_limit = 30 (src/explore_trajectories.py:67-68), a fresh GP per
+    run (mode 0) and all three axes (axes 7; bit i: axis i)."""
+    r = np.zeros(B, EXPLORE_RULE_DTYPE)
+    r["step"], r["desired"], r["v_limit"], r["a_limit"], r["mode"], r["axes"] = step, desired, v_limit, a_limit, mode, axes
+    return r
+
+
+def explore_velocity(env, samples, rules):
+    """The rule on the host, vectorised over B: (explored, v_max, a_max), each [B], from env [B, 3, 2] (min, max of v_body per axis),
+    samples [B] (0: the envelope reads as all zero) and rules [B] of EXPLORE_RULE_DTYPE.  Per axis vabs = 0, raised to max if max > vabs,
+    then to |min| if |min| > vabs; explored = the smallest vabs over the axes of `axes`; v = explored + step if that is < desired, else
+    desired; v_max = v_limit if v > v_limit else v, a_max likewise with a_limit."""
+    env = np.where(np.asarray(samples).reshape(-1, 1, 1) > 0, np.asarray(env, dtype=np.float64), 0.0)
+    mn, mx = env[:, :, 0], env[:, :, 1]
+    vabs = np.zeros(mx.shape)
+    vabs = np.where(mx > vabs, mx, vabs)
+    vabs = np.where(np.abs(mn) > vabs, np.abs(mn), vabs)
+    use = (np.asarray(rules["axes"])[:, None] >> np.arange(3)) & 1 != 0
+    explored = np.where(use, vabs, np.inf).min(axis=1)
+    nxt = explored + rules["step"]
+    v = np.where(nxt < rules["desired"], nxt, rules["desired"])
+    return explored, np.where(v > rules["v_limit"], rules["v_limit"], v), np.where(v > rules["a_limit"], rules["a_limit"], v)
