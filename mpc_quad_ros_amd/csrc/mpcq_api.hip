@@ -186,10 +186,14 @@ bool rgp_axis_constants(const double* X, int nb, double Lh, double sf, double sn
 }  // namespace
 
 // ------------------------------------------------------------------ engine
-// What the trajectory-slot entry points (mpcq_replan, mpcq_replace_trajectories, mpcq_get_trajectories) work on: precision-independent
-// device arrays of the engine (trajectories, cursors and the plant state are float64 in every precision).
-struct TrajSlots {
-  double* traj; int* len; int* idx; int* finished; const double* plant; int Tmax;
+// The precision-independent view of an engine (mpcq_engine::view): what the side launches of a period and the trajectory-slot entry
+// points (mpcq_replan, mpcq_replace_trajectories, mpcq_get_trajectories) work on.  Trajectories, cursors, the plant state, controls, costs
+// and the solver's counters are float64 / int in every precision; only the RGP state and the step kernel's model are not, and stay EngineT's.
+struct EngineView {
+  double* traj; int* len; int* idx; int* finished; const double* plant; int Tmax;   // the trajectory slots and the plant state [B,13]
+  const double* cost; const int* status; const int* qp_iter; const double* w;       // what the last step left: [B], [B], [B], [B,4]
+  int N, skip;
+  double g;
 };
 // Device scratch allocated on first use and replaced by a larger block when a request exceeds it (the contents are not kept).
 // Move-only: declaring the move assignment deletes the copy operations.
@@ -216,8 +220,27 @@ template <typename P> struct DevBuf {
     return err;
   }
 };
-// The flight recorder (mpcq_record_*): host bookkeeping and device buffers of a recording; the launches are EngineT's (rec_snapshot,
-// rec_write).  The selection is kept sorted (a group of mpcq_sim_steps covers a contiguous part of it); pos maps the caller's order to it.
+// buf grown to `elems` elements, or MPCQ_ERR_DEVICE with `message` (the failed allocation's sticky HIP error is cleared: the caller's next
+// HIP call must not meet it)
+template <typename Buf> static int grow_or_fail(Buf& buf, size_t elems, const std::string& message) {
+  if (buf.grow(elems) == hipSuccess) return 0;
+  (void)hipGetLastError();
+  return fail(MPCQ_ERR_DEVICE, message);
+}
+
+// ---- The per-period features.  Each hangs side launches behind the step kernel of every control period (EngineT::period) and is one
+// section here: its state, the layout of its packed device buffers (written once, as accessors) and its launch over an EngineView.  The
+// entry points of each stand in the C ABI part below, under the same heading.  What a period's side launches need to know about the period:
+struct Tick {
+  int row = -1;          // the recorder's row (-1: the period is not recorded)
+  int mper = -1;         // the mission's period number (-1: no mission)
+  long long sper = -1;   // the scoreboard's period number (-1: no score running)
+  long long fper = -1;   // the fleet period of the plant update (-1: no fleet, or no plant update drawn)
+};
+
+// ---- flight recorder (mpcq_record_*, mpcq_record.hpp): host bookkeeping and device buffers of a recording; the launches depend on the
+// precision (record_kernel<T> reads mu and C) and are EngineT's (rec_snapshot, rec_write).  The selection is kept sorted (a group of
+// mpcq_sim_steps covers a contiguous part of it); pos maps the caller's order to it.
 struct Recorder {
   bool on = false;
   int fields = 0, every = 1, capacity = 0, count = 0, rows = 0;
@@ -229,9 +252,20 @@ struct Recorder {
   DevBuf<double> d_f[mpcq::record::NF - 1];   // double fields, [capacity][count][width]
   DevBuf<int> d_solver;                  // [capacity][count][4]
   DevBuf<double> d_snap;                 // [count][SNAP]: x_pred_prev and has_prev in front of the step (MPCQ_RECORD_DRAG)
+  // A period (one fused step of every quadrotor) counts whether it is recorded or not; the row a recorded one writes (-1: not recorded --
+  // no recording, not its turn, or the buffer is full and the period counts as dropped)
+  int next_row() {
+    if (!on) return -1;
+    const long long p = periods++;
+    if (p % every) return -1;
+    if (rows >= capacity) { ++dropped; return -1; }
+    period_of.push_back(p);
+    return rows++;
+  }
 };
-// A device mission (mpcq_mission_*, mpcq_mission.hpp): the queue of upcoming flights, the per-quadrotor leg counters and the log of consumed
-// legs on the device, and what every flight is planned with.  The launch behind a period is mission_launch.
+
+// ---- device missions (mpcq_mission_*, mpcq_mission.hpp): the queue of upcoming flights, the per-quadrotor leg counters and the log of
+// consumed legs on the device, and what every flight is planned with.
 struct Mission {
   bool on = false;
   int L = 0, n_wp = 0, order = 0, nonlinear = 0;
@@ -241,34 +275,113 @@ struct Mission {
   DevBuf<double> d_wp;     // [B,L,n_wp,3] (empty: no waypoint leg)
   DevBuf<mpcq_leg> d_legs; // [B,L]: kind, limits and radius of every leg
   DevBuf<double> d_info;   // [B,6] (nonlinear)
-  DevBuf<int> d_int;       // leg [B] | installed [B] | last_code [B] | claim [B] | leg_code [B,L] | leg_period [B,L]
+  DevBuf<int> d_int;       // ints(B)
+  // The layout of d_int, and of the host image mission_begin fills (nl = B * L): leg [B] | installed [B] | last_code [B] | claim [B] |
+  // leg_code [B,L] | leg_period [B,L]
+  struct Ints { int *leg, *installed, *last_code, *claim, *leg_code, *leg_period; };
+  static size_t n_ints(size_t B, size_t nl) { return 4 * B + 2 * nl; }
+  static Ints ints_at(int* p, size_t B, size_t nl) { return Ints{p, p + B, p + 2 * B, p + 3 * B, p + 4 * B, p + 4 * B + nl}; }
+  Ints ints(size_t B) const { return ints_at(d_int.p, B, B * (size_t)L); }
 };
-// The flight scoreboard (mpcq_score_*, mpcq_score.hpp): one row of 16 doubles per quadrotor and flight slot on the device, folded by a launch
-// behind every period (EngineT::score_write).
+// The mission launch of one period (number `period` since mpcq_mission_set) for the quadrotors [b0, b0 + n) of B on stream s, behind
+// everything the period has issued there.  start [B,13]: where the flights begin (the plant state behind its update, or the period's measurement).
+static void mission_launch(const Mission& ms, const EngineView& t, size_t B, hipStream_t s, int b0, int n, const double* start, int period) {
+  namespace rp = mpcq::replan;
+  rp::MissionArgs a;
+  a.traj = t.traj; a.Tmax = t.Tmax; a.lens = t.len; a.idx = t.idx; a.finished = t.finished;
+  a.start = start; a.wp = ms.d_wp.p; a.legs = ms.d_legs.p;
+  a.L = ms.L; a.n_wp = ms.n_wp; a.order = ms.order;
+  a.dt = ms.dt;
+  a.b0 = b0; a.n = n; a.period = period;
+  const Mission::Ints d = ms.ints(B);
+  a.leg = d.leg; a.installed = d.installed; a.last_code = d.last_code; a.claim = d.claim;
+  a.leg_code = d.leg_code; a.leg_period = d.leg_period;
+  a.info = ms.nonlinear ? ms.d_info.p : nullptr;
+  const mpcq_nl::Opts o = ms.opts;
+  if (ms.nonlinear)
+    hipLaunchKernelGGL(rp::mission_kernel<rp::NlLds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::NlLds>), s, a, o);
+  else
+    hipLaunchKernelGGL(rp::mission_kernel<rp::Lds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::Lds>), s, a, o);
+}
+
+// ---- flight scoreboard (mpcq_score_*, mpcq_score.hpp): one row of 16 doubles per quadrotor and flight slot on the device, folded by a
+// launch behind every period.
 struct Score {
   bool on = false;
   int F = 0, tail_rows = 0;
   long long periods = 0;    // periods issued since mpcq_score_start / mpcq_score_clear
   DevBuf<double> d_table;   // [B,F,16]
-  DevBuf<int> d_int;        // cur [B] | used [B] | overflow [B]
+  DevBuf<int> d_int;        // ints(B)
+  // The layout of d_int: cur [B] | used [B] | overflow [B].  (mpcq::score::score_init_kernel takes the block as a whole and zeroes
+  // 3 * B ints: the one other place that knows it.)
+  struct Ints { int *cur, *used, *overflow; };
+  static size_t n_ints(size_t B) { return 3 * B; }
+  Ints ints(size_t B) const { return Ints{d_int.p, d_int.p + B, d_int.p + 2 * B}; }
 };
-// The fleet (mpcq_fleet_*, mpcq_fleet.hpp): every quadrotor its own plant.  The table as the caller set it (what mpcq_fleet_get returns) and
-// its field-major device form; the launch is EngineT::plant_launch, in the place of the shared plant's.
+// behind the recorder's row, in front of any plant launch: period `sper` of the scoreboard for the quadrotors [b0, b0 + n) of B
+static void score_launch(const Score& sc, const EngineView& v, size_t B, hipStream_t s, int b0, int n, long long sper, const double* xmeas) {
+  mpcq::score::Args a;
+  const Score::Ints d = sc.ints(B);
+  a.table = sc.d_table.p; a.cur = d.cur; a.used = d.used; a.overflow = d.overflow;
+  a.F = sc.F; a.tail_rows = sc.tail_rows; a.b0 = b0; a.n = n; a.period = (double)sper;
+  a.xmeas = xmeas; a.cost = v.cost; a.traj = v.traj;
+  a.tlen = v.len; a.idx = v.idx; a.finished = v.finished; a.status = v.status; a.qp_iter = v.qp_iter;
+  a.Tmax = v.Tmax; a.N = v.N; a.skip = v.skip;
+  hipLaunchKernelGGL(mpcq::score::score_kernel, dim3(mpcq::score::grid((long)n * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, a);
+}
+
+// ---- exploration (mpcq_explore_*, mpcq_explore.hpp): the rules, the envelope of every quadrotor and the log of the limits it chose, on
+// the device.  On only while a mission is: it writes into the mission's legs table (end_exploration).
+struct Explore {
+  bool on = false;
+  DevBuf<mpcq_explore_rule> d_rules;   // [B]
+  DevBuf<unsigned char> d_mask;        // [B,L]
+  DevBuf<double> d_f64;                // f64(B)
+  DevBuf<int64_t> d_samples;           // [B]
+  // The layout of d_f64, and of the host image mpcq_explore_start fills (nl = B * L): env [B,3,2] | leg_limits [B,L,3]
+  struct F64 { double *env, *leg_limits; };
+  static size_t n_f64(size_t B, size_t nl) { return B * 6 + nl * 3; }
+  static F64 f64_at(double* p, size_t B) { return F64{p, p + B * 6}; }
+  F64 f64(size_t B) const { return f64_at(d_f64.p, B); }
+};
+// behind the score's launch, in front of the plant and mission launches: the period's sample into the envelopes of the quadrotors
+// [b0, b0 + n) of B and the limits of the legs the mission launch of this period is about to plan (mpcq_explore.hpp)
+static void explore_launch(const Explore& ex, const Mission& ms, const EngineView& v, size_t B, hipStream_t s, int b0, int n, const double* xmeas) {
+  mpcq::explore::Args a;
+  const Explore::F64 d = ex.f64(B);
+  a.env = d.env; a.leg_limits = d.leg_limits; a.samples = ex.d_samples.p;
+  a.rules = ex.d_rules.p; a.leg_mask = ex.d_mask.p;
+  a.legs = ms.d_legs.p; a.leg = ms.ints(B).leg; a.L = ms.L;
+  a.idx = v.idx; a.finished = v.finished; a.xmeas = xmeas;
+  a.b0 = b0; a.n = n;
+  hipLaunchKernelGGL(mpcq::explore::explore_kernel, dim3(mpcq::explore::grid(n)), dim3(mpcq::explore::BLOCK), 0, s, a);
+}
+
+// ---- the fleet (mpcq_fleet_*, mpcq_fleet.hpp): every quadrotor its own plant.  The table as the caller set it (what mpcq_fleet_get
+// returns) and its field-major device form.
 struct Fleet {
   bool on = false;
   long long period = 0;            // plant updates since period0 was set
   std::vector<mpcq_plant> plants;  // [B]
   DevBuf<double> d_tab;            // [fleet::NF][B]
 };
-// Exploration (mpcq_explore_*, mpcq_explore.hpp): the rules, the envelope of every quadrotor and the log of the limits it chose, on the
-// device; the launch is EngineT::explore_write, between the score's launch and the plant's.  On only while a mission is (it writes into
-// the mission's legs table).
-struct Explore {
-  bool on = false;
-  DevBuf<mpcq_explore_rule> d_rules;   // [B]
-  DevBuf<unsigned char> d_mask;        // [B,L]
-  DevBuf<double> d_f64;                // env [B,3,2] | leg_limits [B,L,3]
-  DevBuf<int64_t> d_samples;           // [B]
+// The fleet's plant update of the quadrotors [b0, b0 + n) of B, fleet period fper, in the place of the shared plant's launch
+// (EngineT::plant_launch): n_sub substeps of sim_dt on xs [B,13] with the controls of the last step.
+static void fleet_launch(const Fleet& fl, const EngineView& v, int B, hipStream_t s, int b0, int n, double* xs, int n_sub, double sim_dt, long long fper) {
+  mpcq::fleet::Args a;
+  a.tab = fl.d_tab.p; a.B = B; a.b0 = b0; a.n = n; a.g = v.g; a.period = (double)fper;
+  a.xs = xs; a.w = v.w; a.n_sub = n_sub; a.sim_dt = sim_dt;
+  hipLaunchKernelGGL(mpcq::fleet::fleet_plant_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a);
+}
+
+// ---- staging of the replan entry points (mpcq_replan, mpcq_replan_nonlinear, mpcq_replan_circle) and of mpcq_replace_trajectories
+struct ReplanStaging {
+  DevBuf<double> d_in;    // replan: the caller's part (waypoints [B,n_wp,3], or radius [B] | v_max [B]) | starts [B,3] | extra; replace: the rows
+  DevBuf<int> d_int;      // ints(B)
+  // The layout of d_int.  A replan: mask [B] | result codes [B].  mpcq_replace_trajectories: indices [B] | lengths [B], in the same places.
+  struct Ints { int *mask, *code, *idx, *len; };
+  static size_t n_ints(size_t B) { return 2 * B; }
+  Ints ints(size_t B) const { return Ints{d_int.p, d_int.p + B, d_int.p, d_int.p + B}; }
 };
 // Quadrotors [b0, b0 + n) that advance by one launch per period: the stream their periods are issued on and, for a group of mpcq_sim_steps
 // on a stream of its own, the event that marks the end of its part of a call.
@@ -315,17 +428,24 @@ struct mpcq_engine : EngineQueues {
   double ktime = 0, kmin = 0, kmax = 0;   // HIP-event time of the timed step-kernel launches: total, fastest, slowest
   int klaunches = 0;
   bool have_sim = false;         // mpcq_sim_reset has set the plant state
-  // staging of mpcq_replan / mpcq_replace_trajectories
-  DevBuf<double> d_rp_in;        // waypoints [B,n_wp,3] | starts [B,3], or the rows of mpcq_replace_trajectories
-  DevBuf<int> d_rp_int;          // [3B]: mask | result codes | indices + lengths of mpcq_replace_trajectories
+  ReplanStaging rp;              // mpcq_replan* / mpcq_replace_trajectories
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
   Mission ms;                    // mpcq_mission_set .. mpcq_mission_stop
-  int mission_next_period() { return ms.on ? (int)ms.periods++ : -1; }   // the number of the period about to be issued (-1: no mission)
   Score sc;                      // mpcq_score_start .. mpcq_score_stop
-  long long score_next_period() { return sc.on ? sc.periods++ : -1; }     // the same for the scoreboard (-1: no score running)
   Fleet fl;                      // mpcq_fleet_set .. mpcq_fleet_stop
-  long long fleet_next_period() { return fl.on ? fl.period++ : -1; }       // the fleet period of the plant update about to be issued (-1: no fleet)
-  Explore ex;                    // mpcq_explore_start .. mpcq_explore_stop (or the end of the mission)
+  Explore ex;                    // mpcq_explore_start .. mpcq_explore_stop (or the end of the mission: end_exploration)
+  // The ticket of the period about to be issued, the one place the features' counters advance.  control: a control period (mpcq_step,
+  // mpcq_step_device_async, every period of mpcq_sim_steps) -- the recorder, the mission and the score count it.  plant: a plant update
+  // (every period of mpcq_sim_steps, mpcq_sim_plant_period) -- the fleet period advances with it, never with a step alone.
+  Tick next_tick(bool control, bool plant) {
+    Tick t;
+    if (control) t = Tick{rec.next_row(), ms.on ? (int)ms.periods++ : -1, sc.on ? sc.periods++ : -1, -1};
+    if (plant && fl.on) t.fper = fl.period++;
+    return t;
+  }
+  // An exploration ends with the mission it explores for, or when that mission's queue is replaced: its launch writes limits into the
+  // mission's legs table, which is gone then.
+  void end_exploration() { ex = Explore(); }
   // RGP read-out (mpcq_rgp_predict / mpcq_record_predict, mpcq_predict.hpp): K_x^-1 as computed at create, in double, and device scratch
   std::vector<double> kxinv64;
   struct PredictScratch {
@@ -340,7 +460,7 @@ struct mpcq_engine : EngineQueues {
     DevBuf<int> pos;
   } tr;
   virtual int rgp_predict(const double* xq, int M, int per_quad, double* mean, double* var) = 0;
-  virtual TrajSlots traj_slots() = 0;
+  virtual EngineView view() = 0;
   virtual int init() = 0;
   virtual int reset() = 0;
   virtual int set_trajectories(const double*, const int32_t*, int32_t) = 0;
@@ -443,28 +563,30 @@ int predict_run(mpcq_engine* e, const TQ* mu, long mu_stride, const TQ* C, long 
   return 0;
 }
 
-// The mission launch of one period (number `period` since mpcq_mission_set) for the quadrotors [b0, b0 + n) on stream s, behind everything
-// the period has issued there.  start [B,13]: where the flights begin (the plant state behind its update, or the period's measurement).
-void mission_launch(mpcq_engine* e, hipStream_t s, int b0, int n, const double* start, int period) {
-  namespace rp = mpcq::replan;
-  const Mission& ms = e->ms;
-  const TrajSlots t = e->traj_slots();
-  const size_t B = e->B;
-  rp::MissionArgs a;
-  a.traj = t.traj; a.Tmax = t.Tmax; a.lens = t.len; a.idx = t.idx; a.finished = t.finished;
-  a.start = start; a.wp = ms.d_wp.p; a.legs = ms.d_legs.p;
-  a.L = ms.L; a.n_wp = ms.n_wp; a.order = ms.order;
-  a.dt = ms.dt;
-  a.b0 = b0; a.n = n; a.period = period;
-  int* d = ms.d_int.p;
-  a.leg = d; a.installed = d + B; a.last_code = d + 2 * B; a.claim = d + 3 * B;
-  a.leg_code = d + 4 * B; a.leg_period = a.leg_code + B * ms.L;
-  a.info = ms.nonlinear ? ms.d_info.p : nullptr;
-  const mpcq_nl::Opts o = ms.opts;
-  if (ms.nonlinear)
-    hipLaunchKernelGGL(rp::mission_kernel<rp::NlLds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::NlLds>), s, a, o);
-  else
-    hipLaunchKernelGGL(rp::mission_kernel<rp::Lds>, dim3(rp::mission_grid(n)), dim3(64), sizeof(rp::MissionLds<rp::Lds>), s, a, o);
+// the check in front of everything that reads the trajectory slots (`who`: the entry point's name)
+int needs_trajectories(mpcq_engine* e, const std::string& who) {
+  if (e->have_traj && e->view().traj) return 0;
+  return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+}
+// the recorder's read-back: rows [rows][count][W] on the device -> out [count][rows][W] in the caller's order
+template <typename V> int rec_read(mpcq_engine* e, const V* src, int W, V* out) {
+  const Recorder& r = e->rec;
+  const size_t n = (size_t)r.rows * r.count * W;
+  if (!n) return 0;
+  std::vector<V> tmp(n);
+  HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(V), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int j = 0; j < r.count; ++j)
+    for (int k = 0; k < r.rows; ++k)
+      std::memcpy(out + ((size_t)j * r.rows + k) * W, tmp.data() + ((size_t)k * r.count + r.pos[j]) * W, W * sizeof(V));
+  return 0;
+}
+// What the five *_stop entry points do with their feature f of e (not_on: the error of a feature that is not on)
+template <typename F> int feature_stop(mpcq_engine* e, F& f, const char* not_on) {
+  if (!f.on) return fail(MPCQ_ERR_STATE, not_on);
+  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the feature's buffers)
+  f = F();
+  return 0;
 }
 
 template <typename T>
@@ -476,7 +598,6 @@ struct EngineT : mpcq_engine {
   int resident_per_cu = 0;   // workgroups of the lockstep instance one CU holds at once (LDS and registers)
   void (*kstep)(const mpcq::DevModel<T>, const mpcq::DevState<T>, const int) = nullptr;
   void (*krun)(const mpcq::DevModel<T>, const mpcq::DevState<T>, const int) = nullptr;   // free-running variant (mpcq_sim_run)
-  std::vector<double> hbufd;
   T *d_basis = nullptr, *d_Kxinv = nullptr, *d_Kx = nullptr;
   double* h_pin = nullptr;   // pinned staging of the host-buffer step: [x_meas B*13 | w B*4 | x_pred B*13]
   double *d_xin = nullptr, *d_uin = nullptr, *d_tmp = nullptr, *d_xs = nullptr, *d_vb = nullptr, *d_ad = nullptr;
@@ -491,7 +612,9 @@ struct EngineT : mpcq_engine {
 
   ~EngineT() override { if (h_pin) (void)hipHostFree(h_pin); }
 
-  TrajSlots traj_slots() override { return TrajSlots{d_traj.p, d_tlen, st.idx, st.finished, d_xs, m.Tmax}; }
+  EngineView view() override {
+    return EngineView{d_traj.p, d_tlen, st.idx, st.finished, d_xs, m.Tmax, st.cost, st.status, st.qp_iter, st.w, N, m.skip, (double)m.g};
+  }
   // a zero-filled device array of n elements (at least one: nb = 0) that lives as long as the engine
   template <typename P> int dalloc(P*& p, size_t n) {
     HIP_TRY(hipMalloc((void**)&p, (n ? n : 1) * sizeof(*p)));
@@ -499,27 +622,22 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemsetAsync(p, 0, (n ? n : 1) * sizeof(*p), stream));
     return 0;
   }
+  // a copy on the engine's stream, complete when the call returns
+  int copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+  }
   int h2q(T* dst, const double* src, size_t n) {
     hbuf.resize(n);
     for (size_t i = 0; i < n; ++i) hbuf[i] = (T)src[i];
-    HIP_TRY(hipMemcpyAsync(dst, hbuf.data(), n * sizeof(T), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
+    return copy_sync(dst, hbuf.data(), n * sizeof(T), hipMemcpyHostToDevice);
   }
-  int h2d(double* dst, const double* src, size_t n) {
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
-  int d2h(double* dst, const double* src, size_t n) {
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
+  int h2d(double* dst, const double* src, size_t n) { return copy_sync(dst, src, n * sizeof(double), hipMemcpyHostToDevice); }
+  int d2h(double* dst, const double* src, size_t n) { return copy_sync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost); }
   int q2h(double* dst, const T* src, size_t n) {
     hbuf.resize(n);
-    HIP_TRY(hipMemcpyAsync(hbuf.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (const int rc = copy_sync(hbuf.data(), src, n * sizeof(T), hipMemcpyDeviceToHost)) return rc;
     for (size_t i = 0; i < n; ++i) dst[i] = (double)hbuf[i];
     return 0;
   }
@@ -821,15 +939,7 @@ struct EngineT : mpcq_engine {
     return 0;
   }
   int base_mode() const { return (cfg.flags & MPCQ_FLAG_STATIC_GP) ? mpcq::MODE_STATIC_GP : 0; }
-  // ---- flight recorder (mpcq_record.hpp).  A period (one fused step of every quadrotor) counts whether it is recorded or not; the row a
-  // recorded one writes (-1: not recorded -- not its turn, or the buffer is full and the period counts as dropped)
-  int rec_next_row() {
-    const long long p = rec.periods++;
-    if (p % rec.every) return -1;
-    if (rec.rows >= rec.capacity) { ++rec.dropped; return -1; }
-    rec.period_of.push_back(p);
-    return rec.rows++;
-  }
+  // ---- flight recorder (mpcq_record.hpp): the two launches that read the RGP state in the engine's precision
   // in front of the step launch: what compute_a_drag of the step compares against (the post phase overwrites it), selection part [j0, j1)
   void rec_snapshot(hipStream_t s, int j0, int j1) {
     const int n = j1 - j0;
@@ -858,38 +968,12 @@ struct EngineT : mpcq_engine {
     a.Tmax = m.Tmax; a.N = N; a.skip = m.skip; a.nb = nb; a.dt_pred = m.dt_pred;
     hipLaunchKernelGGL(mpcq::record::record_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
   }
-  // behind the recorder's row, in front of any plant launch: period `sper` of the scoreboard for the quadrotors [b0, b0 + n)
-  void score_write(hipStream_t s, int b0, int n, long long sper, const double* xmeas) {
-    mpcq::score::Args a;
-    a.table = sc.d_table.p; a.cur = sc.d_int.p; a.used = a.cur + B; a.overflow = a.cur + 2 * (size_t)B;
-    a.F = sc.F; a.tail_rows = sc.tail_rows; a.b0 = b0; a.n = n; a.period = (double)sper;
-    a.xmeas = xmeas; a.cost = st.cost; a.traj = st.traj;
-    a.tlen = st.tlen; a.idx = st.idx; a.finished = st.finished; a.status = st.status; a.qp_iter = st.qp_iter;
-    a.Tmax = m.Tmax; a.N = N; a.skip = m.skip;
-    hipLaunchKernelGGL(mpcq::score::score_kernel, dim3(mpcq::score::grid((long)n * mpcq::score::W)), dim3(mpcq::score::BLOCK), 0, s, a);
-  }
-  // behind the score's launch, in front of the plant and mission launches: the period's sample into the envelopes of the quadrotors
-  // [b0, b0 + n) and the limits of the legs the mission launch of this period is about to plan (mpcq_explore.hpp)
-  void explore_write(hipStream_t s, int b0, int n, const double* xmeas) {
-    mpcq::explore::Args a;
-    a.env = ex.d_f64.p; a.leg_limits = a.env + (size_t)B * 6; a.samples = ex.d_samples.p;
-    a.rules = ex.d_rules.p; a.leg_mask = ex.d_mask.p;
-    a.legs = ms.d_legs.p; a.leg = ms.d_int.p; a.L = ms.L;
-    a.idx = st.idx; a.finished = st.finished; a.xmeas = xmeas;
-    a.b0 = b0; a.n = n;
-    hipLaunchKernelGGL(mpcq::explore::explore_kernel, dim3(mpcq::explore::grid(n)), dim3(mpcq::explore::BLOCK), 0, s, a);
-  }
   // The plant update of the quadrotors [b0, b0 + n): n_sub substeps of sim_dt on xs [B,13] with the controls st.w.  The engine's shared plant
-  // (plant_kernel), or with a fleet set (fper >= 0: its fleet period) every quadrotor's own (fleet_plant_kernel).
+  // (plant_kernel, which reads the model in the engine's precision), or with a fleet set (fper >= 0: its fleet period) every quadrotor's own
+  // (fleet_launch).  The one place a plant update is launched.
   void plant_launch(hipStream_t s, int b0, int n, double* xs, int n_sub, double sim_dt, long long fper) {
-    if (fper < 0) {
-      hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((n + 63) / 64), dim3(64), 0, s, m, xs + (size_t)b0 * 13, st.w + (size_t)b0 * 4, n_sub, sim_dt, n);
-      return;
-    }
-    mpcq::fleet::Args a;
-    a.tab = fl.d_tab.p; a.B = B; a.b0 = b0; a.n = n; a.g = m.g; a.period = (double)fper;
-    a.xs = xs; a.w = st.w; a.n_sub = n_sub; a.sim_dt = sim_dt;
-    hipLaunchKernelGGL(mpcq::fleet::fleet_plant_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a);
+    if (fper >= 0) return fleet_launch(fl, view(), B, s, b0, n, xs, n_sub, sim_dt, fper);
+    hipLaunchKernelGGL(mpcq::plant_kernel<T>, dim3((n + 63) / 64), dim3(64), 0, s, m, xs + (size_t)b0 * 13, st.w + (size_t)b0 * 4, n_sub, sim_dt, n);
   }
   // one lockstep period of the quadrotors [b0, b0 + nq) on stream `strm`; ev_begin (if any) is recorded in front of the STEP kernel, behind
   // the ordering launch, so that the event pairs of sim_steps time the step kernel alone
@@ -903,59 +987,53 @@ struct EngineT : mpcq_engine {
     if (ev_begin) (void)hipEventRecord(ev_begin, strm);
     hipLaunchKernelGGL(kstep, dim3(nq), dim3(64), lds_bytes, strm, m, so, mode);
   }
-  // One period of groups[gi], the only place that issues one.  On the group's stream, in this order: the recorder's snapshot (row >= 0:
-  // the period is recorded) -> ev_front -> ordering launch -> ev_step -> step kernel -> ev_end -> the recorder's row -> the scoreboard's launch
-  // (sper >= 0: a score is running and this is its period number) -> the exploration launch (an exploration runs and mper >= 0) -> the plant kernel
-  // (plant: s.run_nsub substeps of s.run_dt on s.run_x) -> the mission launch (mper >= 0: a mission is active and this is its period
-  // number; the flights start at the plant state behind its update, or without a plant at the period's measurement).  Every event is
-  // optional.  The caller asks hipGetLastError once it has issued all it has to issue.  fper >= 0: a fleet is set and this is the fleet
-  // period of the plant update, which is then the fleet's launch (plant_launch).
-  int period(int gi, const mpcq::DevState<T>& s, int mode, int row, int mper, long long sper, hipEvent_t ev_front, hipEvent_t ev_step, hipEvent_t ev_end, bool plant,
-             long long fper = -1) {
+  // The optional events of a period (see period)
+  struct PeriodEvents { hipEvent_t front = nullptr, step = nullptr, end = nullptr; };
+  // One period of groups[gi], the only place that issues one.  On the group's stream, in this order:
+  //   the recorder's snapshot (t.row >= 0: the period is recorded) -> ev.front -> ordering launch -> ev.step -> step kernel -> ev.end
+  //   -> the recorder's row -> the scoreboard's launch (t.sper >= 0) -> the exploration launch (an exploration runs and t.mper >= 0)
+  //   -> the plant update (plant: s.run_nsub substeps of s.run_dt on s.run_x; with t.fper >= 0 the fleet's launch, plant_launch)
+  //   -> the mission launch (t.mper >= 0; the flights start at the plant state behind its update, or without a plant at the period's
+  //   measurement).
+  // The caller asks hipGetLastError once it has issued all it has to issue.
+  int period(int gi, const mpcq::DevState<T>& s, int mode, const Tick& t, const PeriodEvents& ev, bool plant) {
     const Group& g = groups[gi];
     if (g.n <= 0) return 0;
-    if (row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
-    if (ev_front) HIP_TRY(hipEventRecord(ev_front, g.stream));
-    launch_period(s, mode, ev_step, g.stream, g.b0, g.n);
-    if (ev_end) HIP_TRY(hipEventRecord(ev_end, g.stream));
-    if (row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], row, s.x_meas);
-    if (sper >= 0) score_write(g.stream, g.b0, g.n, sper, s.x_meas);
-    if (ex.on && mper >= 0) explore_write(g.stream, g.b0, g.n, s.x_meas);
-    if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, fper);
-    if (mper >= 0) mission_launch(this, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, mper);
+    const EngineView v = view();
+    if (t.row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
+    if (ev.front) HIP_TRY(hipEventRecord(ev.front, g.stream));
+    launch_period(s, mode, ev.step, g.stream, g.b0, g.n);
+    if (ev.end) HIP_TRY(hipEventRecord(ev.end, g.stream));
+    if (t.row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], t.row, s.x_meas);
+    if (t.sper >= 0) score_launch(sc, v, B, g.stream, g.b0, g.n, t.sper, s.x_meas);
+    if (ex.on && t.mper >= 0) explore_launch(ex, ms, v, B, g.stream, g.b0, g.n, s.x_meas);
+    if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, t.fper);
+    if (t.mper >= 0) mission_launch(ms, v, B, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, t.mper);
     return 0;
   }
   int solve(const double* x0) override {
     int rc;
     if ((rc = h2d(d_xin, x0, (size_t)B * 13))) return rc;
     st.x_meas = d_xin;
-    if ((rc = period(n_groups, st, 0, -1, -1, -1, ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, 0, Tick{}, PeriodEvents{ev0, nullptr, ev1}, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipStreamSynchronize(stream));
     return chk_after();
   }
-  int get_x(int stage, double* out) override {
-    if (stage < 0 || stage > N) return fail(MPCQ_ERR_INVALID, "stage out of range");
-    // one strided copy of the B rows of this stage (a reference-shaped `for i: get(i,'x')` loop stays O(N B))
-    HIP_TRY(hipMemcpy2DAsync(out, 13 * sizeof(double), st.X + (size_t)stage * 13, (size_t)(N + 1) * 13 * sizeof(double), 13 * sizeof(double), B,
-                             hipMemcpyDeviceToHost, stream));
+  // rows [B][width] of `stage` out of src [B][stages][width]: one strided copy (a reference-shaped `for i: get(i,'x')` loop stays O(N B))
+  int get_stage(const double* src, size_t width, int stages, int stage, double* out) {
+    if (stage < 0 || stage >= stages) return fail(MPCQ_ERR_INVALID, "stage out of range");
+    HIP_TRY(hipMemcpy2DAsync(out, width * sizeof(double), src + stage * width, stages * width * sizeof(double), width * sizeof(double), B, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
   }
-  int get_u(int stage, double* out) override {
-    if (stage < 0 || stage >= N) return fail(MPCQ_ERR_INVALID, "stage out of range");
-    HIP_TRY(hipMemcpy2DAsync(out, 4 * sizeof(double), st.U + (size_t)stage * 4, (size_t)N * 4 * sizeof(double), 4 * sizeof(double), B,
-                             hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
+  int get_x(int stage, double* out) override { return get_stage(st.X, 13, N + 1, stage, out); }
+  int get_u(int stage, double* out) override { return get_stage(st.U, 4, N, stage, out); }
   int get_cost(double* out) override { return d2h(out, st.cost, B); }
   int get_int(int which, int32_t* out) override {
-    const int* src = which == 0 ? st.status : (which == 1 ? st.qp_iter : (which == 2 ? st.idx : (which == 4 ? st.qp_work : st.has_prev)));
-    HIP_TRY(hipMemcpyAsync(out, src, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
+    const int* src = which == 0 ? st.status : (which == 1 ? st.qp_iter : (which == 2 ? st.idx : (which == 4 ? st.qp_work : (which == 5 ? st.finished : st.has_prev))));
+    return copy_sync(out, src, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
   }
   int predict(const double* x, const double* u, double dt, double* out) override {
     int rc;
@@ -987,7 +1065,7 @@ struct EngineT : mpcq_engine {
     return predict_run<T>(this, st.mu, 3L * nb, fixed ? nullptr : st.C, 3L * nb * nb, (size_t)B, nullptr, 0, 1, B, xq, M, per_quad, mean, var);
   }
   int step(const double* x_meas, double* w_out, double* x_pred_out) override {
-    if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_step needs mpcq_set_trajectories first");
+    if (const int rc = needs_trajectories(this, "mpcq_step")) return rc;
     // host buffers go through one pinned staging block so that the three copies are truly asynchronous and the
     // call synchronises once: H2D x_meas -> step kernel -> D2H w, x_pred
     const size_t nx = (size_t)B * 13, nw = (size_t)B * 4;
@@ -996,7 +1074,7 @@ struct EngineT : mpcq_engine {
     HIP_TRY(hipMemcpyAsync(d_xin, h_pin, nx * sizeof(double), hipMemcpyHostToDevice, stream));
     st.x_meas = d_xin;
     int rc;
-    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), score_next_period(), ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, st, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), next_tick(true, false), PeriodEvents{ev0, nullptr, ev1}, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     HIP_TRY(hipMemcpyAsync(h_pin + nx, st.w, nw * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1007,19 +1085,19 @@ struct EngineT : mpcq_engine {
     return chk_after();
   }
   int step_device(const double* d_x, double* d_w) override {
-    if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_step_device_async needs mpcq_set_trajectories first");
+    if (const int rc = needs_trajectories(this, "mpcq_step_device_async")) return rc;
     mpcq::DevState<T> s2 = st;   // measurement and control are float64 in every precision (DevState::x_meas / w)
     s2.x_meas = d_x;
     s2.w_ext = d_w;   // the engine's own control record st.w is written as well (mpcq_get_command, mpcq_sim_plant_period(w = NULL))
     int rc;
-    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), rec.on ? rec_next_row() : -1, mission_next_period(), score_next_period(), ev0, nullptr, ev1, false))) return rc;
+    if ((rc = period(n_groups, s2, mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode(), next_tick(true, false), PeriodEvents{ev0, nullptr, ev1}, false))) return rc;
     HIP_TRY(hipGetLastError());
     timed = true;
     return chk_after();   // (synchronises in the checked build only)
   }
   int sim_reset(const double* x0) override { return h2d(d_xs, x0, (size_t)B * 13); }
   int sim_steps(int K, int n_sub, double sim_dt) override {
-    if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_steps needs mpcq_set_trajectories first");
+    if (const int rc = needs_trajectories(this, "mpcq_sim_steps")) return rc;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
     // HIP events around every 4th step-kernel launch: an event pair between two dependent launches costs dispatch overlap (measured
@@ -1046,14 +1124,12 @@ struct EngineT : mpcq_engine {
     for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(groups[g].stream, gstart, 0));
     int rc;
     for (int k = 0; k < K; ++k) {
-      const int row = rec.on ? rec_next_row() : -1;   // (flight recorder: the launches of a group cover the selection inside it)
-      const int mper = mission_next_period();
-      const long long sper = score_next_period();
-      const long long fper = fleet_next_period();   // (one fleet period per control period: the same for every group)
+      const Tick tick = next_tick(true, true);   // (one ticket per control period, the same for every group: the recorder's launches of a group cover the selection inside it)
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
       for (int g = 0; g < G; ++g) {
-        hipEvent_t* pair = g == 0 && k % stride == 0 ? &kev[2 * (k / stride)] : nullptr;
-        if ((rc = period(g, s2, mode, row, mper, sper, nullptr, pair ? pair[0] : nullptr, pair ? pair[1] : nullptr, split || k == K - 1, fper))) return rc;
+        PeriodEvents ev;
+        if (g == 0 && k % stride == 0) { ev.step = kev[2 * (k / stride)]; ev.end = kev[2 * (k / stride) + 1]; }
+        if ((rc = period(g, s2, mode, tick, ev, split || k == K - 1))) return rc;
       }
     }
     for (int g = 1; g < G; ++g) {
@@ -1076,7 +1152,7 @@ struct EngineT : mpcq_engine {
     return chk_after();
   }
   int sim_run(int K, int n_sub, double sim_dt) override {
-    if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_sim_run needs mpcq_set_trajectories first");
+    if (const int rc = needs_trajectories(this, "mpcq_sim_run")) return rc;
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
     if (ex.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot explore (one persistent launch): mpcq_explore_stop and mpcq_mission_stop first, or use mpcq_sim_steps");
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
@@ -1127,13 +1203,9 @@ struct EngineT : mpcq_engine {
     if (rates && (rc = d2h(rates, c + (size_t)B * 5, (size_t)B * 3))) return rc;
     return 0;
   }
-  int get_finished(int32_t* out) override {
-    HIP_TRY(hipMemcpyAsync(out, st.finished, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-  }
+  int get_finished(int32_t* out) override { return get_int(5, out); }
   int get_chunk(double* out) override {
-    if (!have_traj) return fail(MPCQ_ERR_STATE, "mpcq_get_reference_chunk needs mpcq_set_trajectories first");
+    if (const int rc = needs_trajectories(this, "mpcq_get_reference_chunk")) return rc;
     HIP_TRY(d_cmd.grow((size_t)B * N * 13));
     hipLaunchKernelGGL(mpcq::chunk_kernel<T>, dim3(B), dim3(64), 0, stream, m, st.traj, st.tlen, st.idx, d_cmd.p);
     HIP_TRY(hipGetLastError());
@@ -1142,7 +1214,7 @@ struct EngineT : mpcq_engine {
   int sim_plant(const double* w, int n_sub, double sim_dt) override {
     int rc;
     if (w && (rc = h2d(st.w, w, (size_t)B * 4))) return rc;
-    plant_launch(stream, 0, B, d_xs, n_sub, sim_dt, fleet_next_period());
+    plant_launch(stream, 0, B, d_xs, n_sub, sim_dt, next_tick(false, true).fper);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
@@ -1170,9 +1242,7 @@ struct EngineT : mpcq_engine {
   }
   int get_order(int32_t* out) override {   // the permutation the last lockstep launch used (identity when no order is in use)
     if (!use_order) { for (int b = 0; b < B; ++b) out[b] = b; return 0; }
-    HIP_TRY(hipMemcpyAsync(out, d_order, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
+    return copy_sync(out, d_order, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
   }
   int get_prof(unsigned long long* out) override {
 #if defined(MPCQ_PROFILE) || defined(MPCQ_TRACE_NAN)
@@ -1188,8 +1258,7 @@ struct EngineT : mpcq_engine {
     int rc;
     if (X && (rc = d2h(X, st.X, (size_t)B * (N + 1) * 13))) return rc;
     if (U && (rc = d2h(U, st.U, (size_t)B * N * 4))) return rc;
-    if (mu && nb && (rc = q2h(mu, st.mu, (size_t)B * 3 * nb))) return rc;
-    if (C && nb && (rc = q2h(C, st.C, (size_t)B * 3 * nb * nb))) return rc;
+    if ((rc = get_rgp(mu, C))) return rc;
     if (xpp && (rc = d2h(xpp, st.xpp, (size_t)B * 13))) return rc;
     if (hp && (rc = get_int(3, hp))) return rc;
     if (idx && (rc = get_int(2, idx))) return rc;
@@ -1430,41 +1499,72 @@ int mpcq_set_solver_state(mpcq_engine* e, const int32_t* qp_iter, const double* 
 
 // ---- continuous operation: trajectory slots (mpcq_replan.hpp)
 namespace {
-// What mpcq_replan and mpcq_replan_nonlinear (`who`) share: the argument and state checks, in the order a caller meets them, and the
-// inputs on the device.  limits_ok / limits_rule and opts_ok are the caller's own checks of v_max, a_max, dt and of its options.
+// The argument rules of what plans flights: mpcq_replan and mpcq_replan_nonlinear (through replan_inputs), mpcq_mission_set and
+// mpcq_mission_set_legs (`who`), in the order a caller meets them.  The rules of a queue (L, nonlinear, its size) apply with `queue` only.
+struct PlanArgs {
+  bool has_wp; int n_wp;               // n_wp is checked when there are waypoints
+  bool limits_ok; const char* limits;  // the caller's own check of v_max, a_max and dt, and its rule in words
+  int derivative;
+  bool opts_ok;                        // the caller's own check of its options
+  bool queue = false, L_first = false;
+  int L = 0, nonlinear = 0;
+  size_t B = 0;
+};
+int plan_checks(const std::string& who, const PlanArgs& a) {
+  const bool bad_n_wp = a.has_wp && (a.n_wp < 1 || a.n_wp > mpcq::replan::MAXV - 1), bad_L = a.queue && a.L < 1;
+  // (the one place the callers' orders differ: mpcq_mission_set_legs, where waypoints are optional, has looked at L before n_wp since it
+  //  exists; mpcq_mission_set looks at n_wp first, as the replan calls it grew out of do.  Kept: callers see the message.)
+  if (a.L_first && bad_L) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
+  if (bad_n_wp) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
+  if (bad_L) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
+  if (a.queue && a.nonlinear != 0 && a.nonlinear != 1) return fail(MPCQ_ERR_INVALID, who + ": nonlinear must be 0 or 1");
+  if (!a.limits_ok) return fail(MPCQ_ERR_INVALID, who + ": " + a.limits);
+  if (a.derivative < 2 || a.derivative > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
+  if (!a.opts_ok) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
+  if (a.queue && a.B * (size_t)a.L > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  return 0;
+}
+// What the three replan entry points (`who`) share behind their argument checks: the state checks, in the order a caller meets them, and
+// the staging on the device -- start points, mask and result codes.  The caller's own inputs (`head` doubles: waypoints, or radius and
+// v_max) go to in.head, which it fills itself.
 struct ReplanInputs {
-  TrajSlots t;
-  const double *wp, *start;   // waypoints [B,n_wp,3]; start points [B,start_stride]: the caller's [B,3] or the plant state
+  EngineView t;
+  double* head;               // [head] the caller's inputs
+  const double* start;        // start points [B,start_stride]: the caller's [B,3] or the plant state
   int start_stride;
   const int* mask;            // nullptr: the quadrotors whose finished flag is set
   int* code;                  // [B] result codes
   double* extra;              // `extra` doubles of staging behind the inputs
 };
-int replan_inputs(const char* who_, mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, bool limits_ok, const char* limits_rule,
+int replan_stage(const std::string& who, mpcq_engine* e, const double* start, const int32_t* mask, size_t head, size_t extra, ReplanInputs& in) {
+  if (const int rc = needs_trajectories(e, who)) return rc;
+  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, who + " without start points needs mpcq_sim_reset first (the plant state)");
+  in.t = e->view();
+  const size_t B = e->B;
+  HIP_TRY(e->rp.d_in.grow(head + B * 3 + extra));
+  HIP_TRY(e->rp.d_int.grow(ReplanStaging::n_ints(B)));
+  double* d_in = e->rp.d_in.p;
+  const ReplanStaging::Ints d = e->rp.ints(B);
+  if (start) HIP_TRY(hipMemcpyAsync(d_in + head, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(d.mask, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  in.head = d_in;
+  in.start = start ? d_in + head : in.t.plant;
+  in.start_stride = start ? 3 : 13;
+  in.mask = mask ? d.mask : nullptr;
+  in.code = d.code;
+  in.extra = d_in + head + B * 3;
+  return 0;
+}
+// mpcq_replan and mpcq_replan_nonlinear: the checks, the staging and the waypoints [B,n_wp,3] at in.head
+int replan_inputs(const char* who_, mpcq_engine* e, const double* start, const double* wp, int32_t n_wp, bool limits_ok, const char* limits,
                   int32_t derivative_to_optimize, bool opts_ok, const int32_t* mask, size_t extra, ReplanInputs& in) {
   const std::string who(who_);
   if (!wp) return fail(MPCQ_ERR_INVALID, who + ": null waypoints");
-  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
-  if (!limits_ok) return fail(MPCQ_ERR_INVALID, who + ": v_max, a_max and dt must be " + limits_rule);
-  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
-  if (!opts_ok) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
-  in.t = e->traj_slots();
-  if (!e->have_traj || !in.t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
-  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, who + " without start points needs mpcq_sim_reset first (the plant state)");
-  const size_t B = e->B, nwp = B * n_wp * 3;
-  HIP_TRY(e->d_rp_in.grow(nwp + B * 3 + extra));
-  HIP_TRY(e->d_rp_int.grow(3 * B));
-  double* d_in = e->d_rp_in.p;
-  int* d_int = e->d_rp_int.p;
-  HIP_TRY(hipMemcpyAsync(d_in, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (start) HIP_TRY(hipMemcpyAsync(d_in + nwp, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(d_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  in.wp = d_in;
-  in.start = start ? d_in + nwp : in.t.plant;
-  in.start_stride = start ? 3 : 13;
-  in.mask = mask ? d_int : nullptr;
-  in.code = d_int + B;
-  in.extra = d_in + nwp + B * 3;
+  PlanArgs a{true, n_wp, limits_ok, limits, derivative_to_optimize, opts_ok};
+  if (const int rc = plan_checks(who, a)) return rc;
+  const size_t nwp = (size_t)e->B * n_wp * 3;
+  if (const int rc = replan_stage(who, e, start, mask, nwp, extra, in)) return rc;
+  HIP_TRY(hipMemcpyAsync(in.head, wp, nwp * sizeof(double), hipMemcpyHostToDevice, e->stream));
   return 0;
 }
 }  // namespace
@@ -1473,10 +1573,9 @@ int mpcq_replan(mpcq_engine* e, const double* start, const double* wp, int32_t n
                 double dt, const int32_t* mask, int32_t* out) {
   ENTER(e);
   ReplanInputs in;
-  if (const int rc = replan_inputs("mpcq_replan", e, start, wp, n_wp, v_max > 0 && a_max > 0 && dt > 0, "> 0", derivative_to_optimize, true, mask, 0, in)) return rc;
-  const TrajSlots& t = in.t;
-  hipLaunchKernelGGL(mpcq::replan::replan_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
-                     in.start, in.start_stride, in.wp, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code);
+  if (const int rc = replan_inputs("mpcq_replan", e, start, wp, n_wp, v_max > 0 && a_max > 0 && dt > 0, "v_max, a_max and dt must be > 0", derivative_to_optimize, true, mask, 0, in)) return rc;
+  hipLaunchKernelGGL(mpcq::replan::replan_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, in.t.traj, in.t.Tmax, in.t.len, in.t.idx, in.t.finished,
+                     in.start, in.start_stride, (const double*)in.head, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code);
   HIP_TRY(hipGetLastError());
   if (out) HIP_TRY(hipMemcpyAsync(out, in.code, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1490,14 +1589,13 @@ int mpcq_replan_nonlinear(mpcq_engine* e, const double* start, const double* wp,
   const size_t B = e->B, n_info = B * 6, n_pc = B * n_wp * 33, n_df = B * (n_wp - 1) * 9;   // (used behind the check of n_wp only)
   ReplanInputs in;
   if (const int rc = replan_inputs("mpcq_replan_nonlinear", e, start, wp, n_wp, v_max > 0 && a_max > 0 && dt > 0 && std::isfinite(v_max) && std::isfinite(a_max),
-                                   "finite and > 0", derivative_to_optimize, mpcq_nl::nl_opts_valid(o), mask, n_info + n_pc + n_df, in))
+                                   "v_max, a_max and dt must be finite and > 0", derivative_to_optimize, mpcq_nl::nl_opts_valid(o), mask, n_info + n_pc + n_df, in))
     return rc;
-  const TrajSlots& t = in.t;
   double* d_info = in.extra;
   double* d_pc = d_info + n_info;
   double* d_df = d_pc + n_pc;
-  hipLaunchKernelGGL(mpcq::replan::replan_nl_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::NlLds), e->stream, t.traj, t.Tmax, t.len, t.idx,
-                     t.finished, in.start, in.start_stride, in.wp, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code, o,
+  hipLaunchKernelGGL(mpcq::replan::replan_nl_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::NlLds), e->stream, in.t.traj, in.t.Tmax, in.t.len, in.t.idx,
+                     in.t.finished, in.start, in.start_stride, (const double*)in.head, (int)n_wp, v_max, a_max, (int)derivative_to_optimize, dt, in.mask, in.code, o,
                      info ? d_info : nullptr, pieces ? d_pc : nullptr, d_free && n_df ? d_df : nullptr);
   HIP_TRY(hipGetLastError());
   if (out) HIP_TRY(hipMemcpyAsync(out, in.code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1517,24 +1615,15 @@ int mpcq_replan_circle(mpcq_engine* e, const double* start, const double* radius
   if (kind != MPCQ_CIRCLE_ACC_DEC && kind != MPCQ_CIRCLE_CONSTANT && kind != MPCQ_CIRCLE_ACCELERATING) return fail(MPCQ_ERR_INVALID, who + ": unknown kind");
   if (!(dt > 0 && std::isfinite(dt))) return fail(MPCQ_ERR_INVALID, who + ": dt must be finite and > 0");
   if (kind == MPCQ_CIRCLE_ACCELERATING && !(t_max > 0 && std::isfinite(t_max))) return fail(MPCQ_ERR_INVALID, who + ": t_max must be finite and > 0");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
-  if (!start && !e->have_sim) return fail(MPCQ_ERR_STATE, who + " without start points needs mpcq_sim_reset first (the plant state)");
   const size_t B = e->B;
-  HIP_TRY(e->d_rp_in.grow(B * 5));   // radius [B] | v_max [B] | starts [B,3]
-  HIP_TRY(e->d_rp_int.grow(3 * B));
-  double* d_in = e->d_rp_in.p;
-  int* d_int = e->d_rp_int.p;
-  HIP_TRY(hipMemcpyAsync(d_in, radius, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(d_in + B, v_max, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (start) HIP_TRY(hipMemcpyAsync(d_in + 2 * B, start, B * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(d_int, mask, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  int* d_code = d_int + B;
-  hipLaunchKernelGGL(mpcq::replan::circle_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, t.traj, t.Tmax, t.len, t.idx, t.finished,
-                     start ? (const double*)(d_in + 2 * B) : t.plant, start ? 3 : 13, (const double*)d_in, (const double*)(d_in + B), (int)kind, dt, t_max,
-                     mask ? (const int*)d_int : (const int*)nullptr, d_code);
+  ReplanInputs in;
+  if (const int rc = replan_stage(who, e, start, mask, 2 * B, 0, in)) return rc;   // head: radius [B] | v_max [B]
+  HIP_TRY(hipMemcpyAsync(in.head, radius, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(in.head + B, v_max, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(mpcq::replan::circle_kernel, dim3(e->B), dim3(64), sizeof(mpcq::replan::Lds), e->stream, in.t.traj, in.t.Tmax, in.t.len, in.t.idx, in.t.finished,
+                     in.start, in.start_stride, (const double*)in.head, (const double*)(in.head + B), (int)kind, dt, t_max, in.mask, in.code);
   HIP_TRY(hipGetLastError());
-  if (out) HIP_TRY(hipMemcpyAsync(out, d_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (out) HIP_TRY(hipMemcpyAsync(out, in.code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -1542,8 +1631,8 @@ int mpcq_replan_circle(mpcq_engine* e, const double* start, const double* radius
 int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count, const double* traj, const int32_t* len) {
   ENTER(e);
   if (!idx || !traj || !len) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: null argument");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_replace_trajectories needs mpcq_set_trajectories first");
+  if (const int rc = needs_trajectories(e, "mpcq_replace_trajectories")) return rc;
+  const EngineView t = e->view();
   if (count < 0 || count > e->B) return fail(MPCQ_ERR_INVALID, "mpcq_replace_trajectories: count outside 0..B");
   std::vector<char> seen(e->B, 0);
   for (int j = 0; j < count; ++j) {
@@ -1553,10 +1642,10 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
   }
   if (count == 0) return 0;
   const size_t rows = (size_t)count * t.Tmax * 13;
-  HIP_TRY(e->d_rp_in.grow(rows));
-  HIP_TRY(e->d_rp_int.grow((size_t)3 * e->B));
-  double* d_rows = e->d_rp_in.p;
-  int *d_idx = e->d_rp_int.p, *d_len = d_idx + e->B;
+  HIP_TRY(e->rp.d_in.grow(rows));
+  HIP_TRY(e->rp.d_int.grow(ReplanStaging::n_ints(e->B)));
+  double* d_rows = e->rp.d_in.p;
+  int *d_idx = e->rp.ints(e->B).idx, *d_len = e->rp.ints(e->B).len;
   HIP_TRY(hipMemcpyAsync(d_rows, traj, rows * sizeof(double), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(d_idx, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(d_len, len, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
@@ -1567,7 +1656,7 @@ int mpcq_replace_trajectories(mpcq_engine* e, const int32_t* idx, int32_t count,
   return 0;
 }
 
-// ---- device missions (mpcq_mission.hpp; the launch: mission_launch, behind every period of EngineT::period)
+// ---- device missions (mpcq_mission.hpp; state, layout and launch: Mission, mission_launch)
 namespace {
 // What mpcq_mission_set and mpcq_mission_set_legs (`who`) end in, behind their argument checks: the queue, the legs table, the leg counters
 // and an empty log on the device, the mission on.  wp may be NULL (no waypoint leg; n_wp is 0 then).
@@ -1578,20 +1667,20 @@ int mission_begin(const std::string& who, mpcq_engine* e, const mpcq_leg* legs, 
   if (leg0)
     for (size_t b = 0; b < B; ++b)
       if (leg0[b] < 0 || leg0[b] > L) return fail(MPCQ_ERR_INVALID, who + ": leg0 outside 0..L");
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, who + " needs mpcq_set_trajectories first");
+  if (const int rc = needs_trajectories(e, who)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still read the queue that is replaced)
   Mission& ms = e->ms;
   ms.on = false;
-  e->ex = Explore();   // (an exploration wrote into the table that is replaced)
+  e->end_exploration();
   if (wp) HIP_TRY(ms.d_wp.grow(nl * n_wp * 3));
   else ms.d_wp.release();
   HIP_TRY(ms.d_legs.grow(nl));
-  HIP_TRY(ms.d_int.grow(4 * B + 2 * nl));
+  HIP_TRY(ms.d_int.grow(Mission::n_ints(B, nl)));
   if (nonlinear) HIP_TRY(ms.d_info.grow(B * 6));
-  std::vector<int> h(4 * B + 2 * nl, 0);   // leg | installed | last_code | claim | leg_code | leg_period
-  for (size_t b = 0; b < B; ++b) { h[b] = leg0 ? leg0[b] : 0; h[2 * B + b] = MPCQ_REPLAN_SKIPPED; }
-  for (size_t k = 0; k < nl; ++k) { h[4 * B + k] = MPCQ_REPLAN_SKIPPED; h[4 * B + nl + k] = -1; }
+  std::vector<int> h(Mission::n_ints(B, nl), 0);   // the start values: no flight installed, no leg consumed
+  const Mission::Ints hi = Mission::ints_at(h.data(), B, nl);
+  for (size_t b = 0; b < B; ++b) { hi.leg[b] = leg0 ? leg0[b] : 0; hi.last_code[b] = MPCQ_REPLAN_SKIPPED; }
+  for (size_t k = 0; k < nl; ++k) { hi.leg_code[k] = MPCQ_REPLAN_SKIPPED; hi.leg_period[k] = -1; }
   if (wp) HIP_TRY(hipMemcpyAsync(ms.d_wp.p, wp, nl * n_wp * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(ms.d_legs.p, legs, nl * sizeof(mpcq_leg), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(ms.d_int.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
@@ -1610,17 +1699,12 @@ int mpcq_mission_set(mpcq_engine* e, const double* wp, int32_t L, int32_t n_wp, 
                      int32_t nonlinear, const mpcq_minsnap_nl_options* opts, const int32_t* leg0) {
   ENTER(e);
   const std::string who("mpcq_mission_set");
-  // (the checks of replan_inputs, in its order, plus those of the queue)
   if (!wp) return fail(MPCQ_ERR_INVALID, who + ": null waypoints");
-  if (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
-  if (L < 1) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
-  if (nonlinear != 0 && nonlinear != 1) return fail(MPCQ_ERR_INVALID, who + ": nonlinear must be 0 or 1");
-  if (!(v_max > 0 && a_max > 0 && dt > 0 && std::isfinite(v_max) && std::isfinite(a_max) && std::isfinite(dt)))
-    return fail(MPCQ_ERR_INVALID, who + ": v_max, a_max and dt must be finite and > 0");
-  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
   const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
-  if (nonlinear && !mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
-  if ((size_t)e->B * (size_t)L > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  PlanArgs a{true, n_wp, v_max > 0 && a_max > 0 && dt > 0 && std::isfinite(v_max) && std::isfinite(a_max) && std::isfinite(dt),
+             "v_max, a_max and dt must be finite and > 0", derivative_to_optimize, !nonlinear || mpcq_nl::nl_opts_valid(o)};
+  a.queue = true; a.L = L; a.nonlinear = nonlinear; a.B = e->B;
+  if (const int rc = plan_checks(who, a)) return rc;
   // the special case of mpcq_mission_set_legs: every leg a waypoint leg with the call's limits
   mpcq_leg one;
   one.kind = MPCQ_LEG_WAYPOINTS; one.reserved = 0; one.v_max = v_max; one.a_max = a_max; one.radius = 0.0;
@@ -1632,14 +1716,10 @@ int mpcq_mission_set_legs(mpcq_engine* e, const mpcq_leg* legs, const double* wp
   ENTER(e);
   const std::string who("mpcq_mission_set_legs");
   if (!legs) return fail(MPCQ_ERR_INVALID, who + ": null legs");
-  if (L < 1) return fail(MPCQ_ERR_INVALID, who + ": L must be >= 1");
-  if (wp && (n_wp < 1 || n_wp > mpcq::replan::MAXV - 1)) return fail(MPCQ_ERR_INVALID, who + ": n_wp outside 1..7");
-  if (nonlinear != 0 && nonlinear != 1) return fail(MPCQ_ERR_INVALID, who + ": nonlinear must be 0 or 1");
-  if (!(dt > 0 && std::isfinite(dt))) return fail(MPCQ_ERR_INVALID, who + ": dt must be finite and > 0");
-  if (derivative_to_optimize < 2 || derivative_to_optimize > 4) return fail(MPCQ_ERR_INVALID, who + ": derivative_to_optimize outside 2..4");
   const mpcq_nl::Opts o = mpcq_nl::nl_opts_from(opts);   // (NULL: MPCQ_MINSNAP_NL_DEFAULTS)
-  if (nonlinear && !mpcq_nl::nl_opts_valid(o)) return fail(MPCQ_ERR_INVALID, who + ": options out of range");
-  if ((size_t)e->B * (size_t)L > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": queue too large (B x L x n_wp)");
+  PlanArgs a{wp != nullptr, n_wp, dt > 0 && std::isfinite(dt), "dt must be finite and > 0", derivative_to_optimize, !nonlinear || mpcq_nl::nl_opts_valid(o)};
+  a.queue = true; a.L_first = true; a.L = L; a.nonlinear = nonlinear; a.B = e->B;
+  if (const int rc = plan_checks(who, a)) return rc;
   auto positive = [](double x) { return x > 0 && std::isfinite(x); };
   for (size_t k = 0, nl = (size_t)e->B * (size_t)L; k < nl; ++k) {
     const mpcq_leg& lg = legs[k];
@@ -1656,12 +1736,12 @@ int mpcq_mission_get(mpcq_engine* e, int32_t* leg, int32_t* installed, int32_t* 
   const Mission& ms = e->ms;
   if (!ms.on) return fail(MPCQ_ERR_STATE, "mpcq_mission_get: no mission set");
   const size_t B = e->B, nl = B * (size_t)ms.L;
-  const int* d = ms.d_int.p;
-  if (leg) HIP_TRY(hipMemcpyAsync(leg, d, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (installed) HIP_TRY(hipMemcpyAsync(installed, d + B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (last_code) HIP_TRY(hipMemcpyAsync(last_code, d + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (leg_code) HIP_TRY(hipMemcpyAsync(leg_code, d + 4 * B, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (leg_period) HIP_TRY(hipMemcpyAsync(leg_period, d + 4 * B + nl, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  const Mission::Ints d = ms.ints(B);
+  if (leg) HIP_TRY(hipMemcpyAsync(leg, d.leg, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (installed) HIP_TRY(hipMemcpyAsync(installed, d.installed, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (last_code) HIP_TRY(hipMemcpyAsync(last_code, d.last_code, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (leg_code) HIP_TRY(hipMemcpyAsync(leg_code, d.leg_code, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (leg_period) HIP_TRY(hipMemcpyAsync(leg_period, d.leg_period, nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   if (info && ms.nonlinear) HIP_TRY(hipMemcpyAsync(info, ms.d_info.p, B * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (info && !ms.nonlinear)
@@ -1670,14 +1750,12 @@ int mpcq_mission_get(mpcq_engine* e, int32_t* leg, int32_t* installed, int32_t* 
 }
 int mpcq_mission_stop(mpcq_engine* e) {
   ENTER(e);
-  if (!e->ms.on) return fail(MPCQ_ERR_STATE, "mpcq_mission_stop: no mission set");
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the queue)
-  e->ms = Mission();
-  e->ex = Explore();   // (the table an exploration wrote into is gone)
+  if (const int rc = feature_stop(e, e->ms, "mpcq_mission_stop: no mission set")) return rc;
+  e->end_exploration();
   return 0;
 }
 
-// ---- exploration (mpcq_explore.hpp; the launch: EngineT::explore_write, behind the score's launch of EngineT::period)
+// ---- exploration (mpcq_explore.hpp; state, layout and launch: Explore, explore_launch)
 int mpcq_explore_start(mpcq_engine* e, const mpcq_explore_rule* rules, uint64_t rule_size, const uint8_t* leg_mask, const double* env0, const int64_t* samples0) {
   ENTER(e);
   const std::string who("mpcq_explore_start");
@@ -1701,16 +1779,16 @@ int mpcq_explore_start(mpcq_engine* e, const mpcq_explore_rule* rules, uint64_t 
   // The new state goes to buffers of its own and takes the old one's place only once it is complete on the device: a failed allocation or
   // copy leaves the engine exploring as it did (or not at all).
   Explore fresh;
-  if (fresh.d_rules.grow(B) != hipSuccess || fresh.d_mask.grow(nl) != hipSuccess || fresh.d_f64.grow(B * 6 + nl * 3) != hipSuccess ||
-      fresh.d_samples.grow(B) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MPCQ_ERR_DEVICE, who + ": cannot allocate the rules, the envelopes and the log");
-  }
-  std::vector<double> f64(B * 6 + nl * 3, std::nan(""));   // env | leg_limits (NaN: not written)
+  const std::string no_mem = who + ": cannot allocate the rules, the envelopes and the log";
+  if (grow_or_fail(fresh.d_rules, B, no_mem) || grow_or_fail(fresh.d_mask, nl, no_mem) || grow_or_fail(fresh.d_f64, Explore::n_f64(B, nl), no_mem) ||
+      grow_or_fail(fresh.d_samples, B, no_mem))
+    return MPCQ_ERR_DEVICE;
+  std::vector<double> f64(Explore::n_f64(B, nl), std::nan(""));   // (leg_limits NaN: not written)
+  const Explore::F64 hf = Explore::f64_at(f64.data(), B);
   std::vector<int64_t> smp(B, 0);
   for (size_t b = 0; b < B; ++b) {
     const bool have = samples0 && samples0[b] > 0;   // (samples == 0 reads as min = max = 0)
-    for (int k = 0; k < 6; ++k) f64[b * 6 + k] = have ? env0[b * 6 + k] : 0.0;
+    for (int k = 0; k < 6; ++k) hf.env[b * 6 + k] = have ? env0[b * 6 + k] : 0.0;
     if (have) smp[b] = samples0[b];
   }
   const std::vector<unsigned char> all(leg_mask ? 0 : nl, 1);
@@ -1729,21 +1807,16 @@ int mpcq_explore_get(mpcq_engine* e, double* env, int64_t* samples, double* leg_
   const Explore& ex = e->ex;
   if (!ex.on) return fail(MPCQ_ERR_STATE, "mpcq_explore_get: no exploration running");
   const size_t B = e->B, nl = B * (size_t)e->ms.L;
-  if (env) HIP_TRY(hipMemcpyAsync(env, ex.d_f64.p, B * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (leg_limits) HIP_TRY(hipMemcpyAsync(leg_limits, ex.d_f64.p + B * 6, nl * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  const Explore::F64 d = ex.f64(B);
+  if (env) HIP_TRY(hipMemcpyAsync(env, d.env, B * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (leg_limits) HIP_TRY(hipMemcpyAsync(leg_limits, d.leg_limits, nl * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (samples) HIP_TRY(hipMemcpyAsync(samples, ex.d_samples.p, B * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
-int mpcq_explore_stop(mpcq_engine* e) {
-  ENTER(e);
-  if (!e->ex.on) return fail(MPCQ_ERR_STATE, "mpcq_explore_stop: no exploration running");
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the envelopes)
-  e->ex = Explore();
-  return 0;
-}
+int mpcq_explore_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->ex, "mpcq_explore_stop: no exploration running"); }
 
-// ---- flight recorder (mpcq_record.hpp; the launches: EngineT::rec_snapshot / rec_write)
+// ---- flight recorder (mpcq_record.hpp; state: Recorder; the launches: EngineT::rec_snapshot / rec_write)
 #define MPCQ_RECORD_ALL 511
 int mpcq_record_start(mpcq_engine* e, const int32_t* quads, int32_t count, int32_t fields, int32_t every, int32_t capacity) {
   ENTER(e);
@@ -1773,9 +1846,7 @@ int mpcq_record_start(mpcq_engine* e, const int32_t* quads, int32_t count, int32
   }
   // (a return from here on releases what `nr` holds by then; the engine's recorder is touched by the last statement only)
   auto need = [](auto& buf, size_t elems, const char* what) {
-    if (buf.grow(elems) == hipSuccess) return 0;
-    (void)hipGetLastError();
-    return fail(MPCQ_ERR_DEVICE, std::string("mpcq_record_start: cannot allocate ") + std::to_string(elems * sizeof(*buf.p)) + " bytes for " + what);
+    return grow_or_fail(buf, elems, "mpcq_record_start: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes for " + what);
   };
   int rc = need(nr.d_sel, (size_t)n, "the selection");
   for (int f = 0; f < mpcq::record::NF && !rc; ++f) {
@@ -1802,23 +1873,6 @@ int mpcq_record_info(mpcq_engine* e, int32_t* rows, int64_t* dropped, int64_t* p
   if (periods) *periods = r.periods;
   return 0;
 }
-extern "C++" {
-namespace {
-// rows [rows][count][W] on the device -> out [count][rows][W] in the caller's order
-template <typename V> int rec_read(mpcq_engine* e, const V* src, int W, V* out) {
-  const Recorder& r = e->rec;
-  const size_t n = (size_t)r.rows * r.count * W;
-  if (!n) return 0;
-  std::vector<V> tmp(n);
-  HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(V), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  for (int j = 0; j < r.count; ++j)
-    for (int k = 0; k < r.rows; ++k)
-      std::memcpy(out + ((size_t)j * r.rows + k) * W, tmp.data() + ((size_t)k * r.count + r.pos[j]) * W, W * sizeof(V));
-  return 0;
-}
-}  // namespace
-}  // extern "C++"
 int mpcq_record_get(mpcq_engine* e, int32_t field, double* out) {
   ENTER(e);
   const Recorder& r = e->rec;
@@ -1853,15 +1907,9 @@ int mpcq_record_clear(mpcq_engine* e) {
   r.rows = 0; r.dropped = 0; r.period_of.clear();
   return 0;
 }
-int mpcq_record_stop(mpcq_engine* e) {
-  ENTER(e);
-  if (!e->rec.on) return fail(MPCQ_ERR_STATE, "mpcq_record_stop: no active recording");
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the buffers)
-  e->rec = Recorder();
-  return 0;
-}
+int mpcq_record_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->rec, "mpcq_record_stop: no active recording"); }
 
-// ---- flight scoreboard (mpcq_score.hpp; the launch: EngineT::score_write, behind the recorder's row of every period)
+// ---- flight scoreboard (mpcq_score.hpp; state, layout and launch: Score, score_launch)
 namespace {
 // table, cur, used and overflow to their start values on the engine's stream, and the period count to 0
 int score_init(mpcq_engine* e) {
@@ -1882,17 +1930,13 @@ int mpcq_score_start(mpcq_engine* e, int32_t flights, int32_t tail_rows) {
   ENTER(e);
   if (flights < 1 || tail_rows < 0) return fail(MPCQ_ERR_INVALID, "mpcq_score_start: flights must be >= 1 and tail_rows >= 0");
   if ((size_t)e->B * (size_t)flights * mpcq::score::W > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "mpcq_score_start: table too large (B x flights x 16)");
-  if (!e->have_traj) return fail(MPCQ_ERR_STATE, "mpcq_score_start needs mpcq_set_trajectories first");
+  if (const int rc = needs_trajectories(e, "mpcq_score_start")) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the table that is replaced)
   Score& sc = e->sc;
   sc.on = false;
-  auto need = [](auto& buf, size_t elems) {
-    if (buf.grow(elems) == hipSuccess) return 0;
-    (void)hipGetLastError();
-    return fail(MPCQ_ERR_DEVICE, "mpcq_score_start: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes");
-  };
+  auto need = [](auto& buf, size_t elems) { return grow_or_fail(buf, elems, "mpcq_score_start: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes"); };
   int rc;
-  if ((rc = need(sc.d_table, (size_t)e->B * flights * mpcq::score::W)) || (rc = need(sc.d_int, (size_t)e->B * 3))) return rc;
+  if ((rc = need(sc.d_table, (size_t)e->B * flights * mpcq::score::W)) || (rc = need(sc.d_int, Score::n_ints(e->B)))) return rc;
   sc.F = flights; sc.tail_rows = tail_rows;
   if ((rc = score_init(e))) return rc;
   sc.on = true;
@@ -1904,8 +1948,8 @@ int mpcq_score_get(mpcq_engine* e, double* score, int32_t* flights, int32_t* ove
   if (!sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_get: no score running");
   const size_t B = e->B;
   if (score) HIP_TRY(hipMemcpyAsync(score, sc.d_table.p, B * sc.F * mpcq::score::W * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (flights) HIP_TRY(hipMemcpyAsync(flights, sc.d_int.p + B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (overflow) HIP_TRY(hipMemcpyAsync(overflow, sc.d_int.p + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (flights) HIP_TRY(hipMemcpyAsync(flights, sc.ints(B).used, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (overflow) HIP_TRY(hipMemcpyAsync(overflow, sc.ints(B).overflow, B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (periods) *periods = sc.periods;
   return 0;
@@ -1915,15 +1959,9 @@ int mpcq_score_clear(mpcq_engine* e) {
   if (!e->sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_clear: no score running");
   return score_init(e);
 }
-int mpcq_score_stop(mpcq_engine* e) {
-  ENTER(e);
-  if (!e->sc.on) return fail(MPCQ_ERR_STATE, "mpcq_score_stop: no score running");
-  HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still write the table)
-  e->sc = Score();
-  return 0;
-}
+int mpcq_score_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->sc, "mpcq_score_stop: no score running"); }
 
-// ---- the fleet (mpcq_fleet.hpp; the launch: EngineT::plant_launch, in the place of the shared plant's launch of a period)
+// ---- the fleet (mpcq_fleet.hpp; state and launch: Fleet, fleet_launch, in the place of the shared plant's launch: EngineT::plant_launch)
 int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants, uint64_t plant_size, int64_t period0) {
   ENTER(e);
   namespace ft = mpcq::fleet;
@@ -1960,10 +1998,7 @@ int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants, uint64_t plant_size
   // The new table goes to a buffer of its own and takes the old one's place only once it is complete on the device: a failed allocation
   // or copy leaves the engine flying the table it had.
   DevBuf<double> fresh;
-  if (fresh.grow(tab.size()) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(MPCQ_ERR_DEVICE, "mpcq_fleet_set: cannot allocate " + std::to_string(tab.size() * sizeof(double)) + " bytes");
-  }
+  if (const int rc = grow_or_fail(fresh, tab.size(), "mpcq_fleet_set: cannot allocate " + std::to_string(tab.size() * sizeof(double)) + " bytes")) return rc;
   HIP_TRY(hipMemcpyAsync(fresh.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));   // (behind it nothing the engine has enqueued reads the table that is replaced: the calls that launch the plant return synchronised)
   fl.d_tab = std::move(fresh);
@@ -1982,13 +2017,7 @@ int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants, uint64_t plant_size, int6
   if (period) *period = fl.period;
   return 0;
 }
-int mpcq_fleet_stop(mpcq_engine* e) {
-  ENTER(e);
-  if (!e->fl.on) return fail(MPCQ_ERR_STATE, "mpcq_fleet_stop: no fleet set");
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->fl = Fleet();
-  return 0;
-}
+int mpcq_fleet_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->fl, "mpcq_fleet_stop: no fleet set"); }
 
 // ---- RGP read-out (mpcq_predict.hpp; predict_run).  The engine's stream is behind every group stream of mpcq_sim_steps when that call
 // returns, and both calls run on it: they see the state after the last period.
@@ -2083,11 +2112,7 @@ int train_run(mpcq_engine* e, const mpcq_train_spec* sp, int nb, const double* v
   const bool learn = sp->mode == MPCQ_TRAIN_LEARN, own = sp->nb == 0;
   const size_t n = nb, nn = n * n, R = (size_t)S * 3;
   if (R > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, "RGP training: too many streams for one call");
-  auto need = [](auto& buf, size_t elems) {
-    if (buf.grow(elems) == hipSuccess) return 0;
-    (void)hipGetLastError();
-    return fail(MPCQ_ERR_DEVICE, "RGP training: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes");
-  };
+  auto need = [](auto& buf, size_t elems) { return grow_or_fail(buf, elems, "RGP training: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes"); };
   int rc;
   // the model on the device: theta | K_x (the start value of C) | basis | K_x^-1
   const double* basis_h = own ? e->basis.data() : sp->basis;
@@ -2155,7 +2180,7 @@ int mpcq_rgp_train(mpcq_engine* e, const mpcq_train_spec* sp, const double* v_bo
   if (S < 1) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_train: S must be >= 1");
   if (T < 1 + sp->pair_next) return fail(MPCQ_ERR_INVALID, "mpcq_rgp_train: T must be >= 1 (>= 2 with pair_next)");
   const size_t cnt = (size_t)S * T * 3;
-  if (e->tr.in.grow(2 * cnt) != hipSuccess) { (void)hipGetLastError(); return fail(MPCQ_ERR_DEVICE, "mpcq_rgp_train: cannot allocate the sample buffer"); }
+  if (const int rc = grow_or_fail(e->tr.in, 2 * cnt, "mpcq_rgp_train: cannot allocate the sample buffer")) return rc;
   HIP_TRY(hipMemcpyAsync(e->tr.in.p, v_body, cnt * sizeof(double), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->tr.in.p + cnt, a_drag, cnt * sizeof(double), hipMemcpyHostToDevice, e->stream));
   return train_run(e, sp, nb, e->tr.in.p, e->tr.in.p + cnt, 3L * T, 3, nullptr, S, T, out);
@@ -2175,8 +2200,8 @@ int mpcq_record_train(mpcq_engine* e, const mpcq_train_spec* sp, int32_t row0, i
 
 int mpcq_get_trajectories(mpcq_engine* e, double* traj, int32_t* len) {
   ENTER(e);
-  const TrajSlots t = e->traj_slots();
-  if (!e->have_traj || !t.traj) return fail(MPCQ_ERR_STATE, "mpcq_get_trajectories needs mpcq_set_trajectories first");
+  if (const int rc = needs_trajectories(e, "mpcq_get_trajectories")) return rc;
+  const EngineView t = e->view();
   if (traj) HIP_TRY(hipMemcpyAsync(traj, t.traj, (size_t)e->B * t.Tmax * 13 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (len) HIP_TRY(hipMemcpyAsync(len, t.len, (size_t)e->B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));

@@ -1,7 +1,7 @@
 // mpcq_fleet.hpp — the fleet (mpcq_fleet_set / _get / _stop): every quadrotor its own plant.  Included from mpcq_api.hip only, after
 // mpcq_kernels.hpp; the step kernel, its state and plant_kernel are untouched.
 //
-//  * fleet_plant_kernel takes the place of plant_kernel in a period (EngineT::period, EngineT::sim_plant) while a fleet is set: behind the
+//  * fleet_plant_kernel takes the place of plant_kernel in a period (fleet_launch, from EngineT::plant_launch) while a fleet is set: behind the
 //    recorder's row and the score, in front of the mission launch.  Same mapping: one lane per quadrotor, blocks of one wavefront.
 //  * The table lives on the device field-major, tab[field * B + b]: the 64 lanes of a wavefront load 64 neighbouring doubles per field
 //    (one mpcq_plant as an array of structs would put the lanes 264 bytes apart).  A launch over the group [b0, b0 + n) indexes it with

@@ -21,7 +21,7 @@ namespace mpcq {
 namespace replan {
 
 struct MissionArgs {
-  double* traj; int Tmax; int *lens, *idx, *finished;   // the trajectory slots (TrajSlots)
+  double* traj; int Tmax; int *lens, *idx, *finished;   // the trajectory slots (EngineView)
   const double* start;        // [B,13]: the plant state behind the period's update, or the period's measurement
   const double* wp;           // [B,L,n_wp,3] (not read for a circle leg; nullptr if the queue has no waypoint leg)
   const mpcq_leg* legs;       // [B,L]: kind, limits and radius of every leg (mpcq_mission_set: the same waypoint leg everywhere)
