@@ -394,7 +394,8 @@ int mpcq_get_trajectories(mpcq_engine* e, double* traj /*[B,Tmax,13] or NULL*/, 
  * points a host loop `sim_steps(1); replan(mask = finished & (leg < L))` passes, and the results are bit for bit that loop's.  The leg
  * is consumed whatever the MPCQ_REPLAN_* code: a negative code leaves trajectory, cursor and flag as they were and the next period
  * tries the next leg.  A quadrotor whose queue is exhausted (leg[b] == L) holds its last reference row, as without a mission.
- * On the stream of a period the order is: recorder snapshot -> ordering launch -> step -> recorder row -> plant -> mission; a recorded
+ * On the stream of a period the order is: recorder snapshot -> black-box snapshot -> ordering launch -> step -> recorder row ->
+ * black box -> score -> exploration -> plant -> mission (each only while its feature is on); a recorded
  * row of the finishing period shows finished = 1 and the old cursor, the next row cursor 0 of the new flight.  While a mission is
  * active every plant update of mpcq_sim_steps is a launch of its own (same arithmetic, same results as the fused form).
  * mpcq_sim_run (one persistent launch) flies no mission: MPCQ_ERR_STATE while one is active.  Host calls of mpcq_replan* and
@@ -467,13 +468,76 @@ int mpcq_record_clear(mpcq_engine* e);
 /* frees the buffers; recording off.  get / info / clear / stop without an active recording: MPCQ_ERR_STATE. */
 int mpcq_record_stop(mpcq_engine* e);
 
+/* ---- incident recorder: a black box per quadrotor.  In a sweep that flies as one batch some quadrotors get lost, and which ones is not
+ * known beforehand.  The scoreboard shows that something went wrong, the flight recorder shows what -- but only for quadrotors chosen
+ * before the run, with memory that grows with its length.  A black box watches `count` quadrotors (quads, or all B): each gets a ring of
+ * D = pre + 1 + post of the flight recorder's rows, overwritten every period, and a rule of its own that is judged on the device; the
+ * ring stops `post` periods after the rule first fires.  Memory: count x D x (sum of the widths) x 8 bytes, whatever the length of the
+ * run, and no host round trip.  The fields are the flight recorder's MPCQ_RECORD_* bits, with its widths and its float64 storage.
+ *   Periods p = 0, 1, ... count from mpcq_blackbox_start as the flight recorder counts them: one mpcq_step / mpcq_step_device_async
+ * call, one iteration of mpcq_sim_steps / mpcq_sim_control_periods; mpcq_solve is not a period.
+ *   Per watched quadrotor the device keeps state (0 armed, 1 fired, 2 frozen), fired_period (-1), cause (0), left and first (the first
+ * period whose row the ring holds).  In period p, for a quadrotor that is not frozen:
+ *  1. Its row of every requested field goes to ring slot p % D: bit for bit the values the flight recorder writes for that period
+ *     (MPCQ_RECORD_DRAG against the x_pred_prev the step started from, MPCQ_RECORD_X_REF row 0 of the chunk the step used).
+ *  2. The rule is judged on the period's values and gives a cause word c.  Armed and c != 0: fired_period = p, cause = c, state = 1,
+ *     left = post.  Already in state 1 before this period: left -= 1.  In state 1 with left == 0: state = 2 (with post = 0, in the
+ *     firing period itself).
+ * A frozen quadrotor's ring is no longer written: it holds exactly the periods max(first, f - pre) .. f + post of the first incident.
+ *   Causes (bits of rule.causes; a cause that is not enabled is never raised; all causes true in the firing period are reported together),
+ * with x the measurement the step solved from, ref the MPCQ_RECORD_X_REF row, w the control and cost the cost of the step: */
+#define MPCQ_BB_STATUS     1   /* status & rule.status_mask is non-zero */
+#define MPCQ_BB_FALLBACK   2   /* the period's solve was a fallback solve: qp_iter / 1000 % 10 != 0 (the scoreboard's `fallbacks`) */
+#define MPCQ_BB_NONFINITE  4   /* any entry of x, w or the cost is not finite */
+#define MPCQ_BB_ERR_POS    8   /* ((dx*dx + dy*dy) + dz*dz) > err_pos*err_pos, d = x[0:3] - ref[0:3] */
+#define MPCQ_BB_SPEED     16   /* ((vx*vx + vy*vy) + vz*vz) > speed*speed, v = x[7:10] */
+#define MPCQ_BB_TILT      32   /* 1 - 2*(qx*qx + qy*qy) < tilt_cos (body z against world z), q = x[3:7] */
+#define MPCQ_BB_COST      64   /* cost > rule.cost */
+/* The sums of squares and the tilt expression are evaluated in the order written, every operation rounded on its own (no fused
+ * multiply-add), so a host reproduces them exactly from recorded rows.  A comparison with a NaN operand is false: NaN is what
+ * MPCQ_BB_NONFINITE is for.
+ *   The black box changes no result: with it on or off every state, output and statistic is bit-identical, and so is every row of a
+ * flight recorder or scoreboard running next to it.  It runs together with the recorder, score, mission, exploration and fleet and does
+ * not depend on mpcq_tuning.groups; mpcq_reset, mpcq_set_state and the replan calls are legal while it runs.  On the stream of a period
+ * the order is: recorder snapshot -> black-box snapshot -> ordering launch -> step -> recorder row -> black box -> score -> exploration
+ * -> plant -> mission.  mpcq_sim_run (one persistent launch) keeps no black box: MPCQ_ERR_STATE while one runs.  A black box is per
+ * engine (per shard) and not part of a checkpoint, like a recording. */
+typedef struct mpcq_blackbox_rule { int32_t causes, status_mask; double err_pos, speed, tilt_cos, cost; } mpcq_blackbox_rule;   /* one per watched quadrotor */
+/* Starts a black box for quadrotors quads[0..count) (NULL: all B, count ignored) with rules [count] in the same order.
+ * MPCQ_ERR_STATE: a black box runs.  MPCQ_ERR_INVALID, with the engine left as it was: count <= 0 with quads, an index out of range or
+ * twice, fields 0 or unknown bits, an RGP field with nb = 0, pre or post negative, D > 65536, rules NULL, and -- mpcq_last_error() names
+ * the quadrotor and the field -- unknown cause bits, a NaN threshold of an enabled cause, err_pos or speed < 0.  MPCQ_ERR_DEVICE: the
+ * buffers cannot be allocated. */
+int mpcq_blackbox_start(mpcq_engine* e, const int32_t* quads /*[count] or NULL*/, int32_t count, int32_t fields, int32_t pre, int32_t post,
+                        const mpcq_blackbox_rule* rules /*[count], caller's order*/);
+/* The state of every watched quadrotor in the caller's order, behind everything the engine has enqueued; any pointer may be NULL.
+ * rows [count]: min(D, periods written since first) -- for a quadrotor that has fired, the rows of its incident so far: the periods
+ * max(first, f - pre) .. min(f + post, the last period); fired_row [count]: the index of the firing row in the time-ordered read-out
+ * (-1: not fired); periods: periods counted since mpcq_blackbox_start. */
+int mpcq_blackbox_info(mpcq_engine* e, int64_t* fired_period, int32_t* cause, int32_t* state, int32_t* rows, int32_t* fired_row /*each [count] or NULL*/,
+                       int64_t* periods);
+/* The rings of a subset, gathered on the device into time order and left-aligned: which [n] are positions in the selection (the caller's
+ * order of mpcq_blackbox_start; NULL: the whole selection, n ignored), out [n, D, width] for one double field (a single MPCQ_RECORD_*
+ * bit of the black box other than MPCQ_RECORD_SOLVER).  Row k of item i is period first_row_period + k; rows beyond rows[i] are NaN
+ * (-1 for the solver ints and the period numbers).  Only n rings travel to the host.  MPCQ_ERR_INVALID: a field the black box does not
+ * keep, a position outside [0, count) or twice. */
+int mpcq_blackbox_get(mpcq_engine* e, int32_t field, const int32_t* which /*[n] positions in the selection, or NULL: all*/, int32_t n, double* out /*[n, D, width]*/);
+int mpcq_blackbox_get_solver(mpcq_engine* e, const int32_t* which, int32_t n, int32_t* out /*[n, D, 4]*/);
+int mpcq_blackbox_get_periods(mpcq_engine* e, const int32_t* which, int32_t n, int64_t* out /*[n, D]*/);
+/* The selected quadrotors (mask [count] non-zero, caller's order; NULL: all) back to armed with an empty ring: first = the next period,
+ * fired_period = -1, cause = 0.  The others keep what they hold. */
+int mpcq_blackbox_rearm(mpcq_engine* e, const int32_t* mask /*[count] or NULL*/);
+/* frees the buffers; black box off, period launches are what they are without one.  Every call but mpcq_blackbox_start without a
+ * running black box: MPCQ_ERR_STATE. */
+int mpcq_blackbox_stop(mpcq_engine* e);
+
 /* ---- flight scoreboard (since 0.6.7): the reference evaluates a run flight by flight -- src/compare_trajectories.py:40-51 plots, per
  * flight, max ||v|| against the mean of the per-step rms_pos of src/Visualiser.py:805-822 and leaves out the last second "because it
  * tries to stop in place".  Here a table score [B, F, 16] of doubles lives on the device and one small launch behind every period folds
  * that period into the row of the flight the quadrotor is flying; the host reads the table once, at the end of a sweep.  A period is
  * what the flight recorder and the missions count: one mpcq_step / mpcq_step_device_async call, one iteration of mpcq_sim_steps /
- * mpcq_sim_control_periods; mpcq_solve is not a period.  On the stream of a period the order is: recorder snapshot -> ordering launch ->
- * step -> recorder row -> score -> plant -> mission, so the score reads what a recorded row shows: the measurement x the step solved
+ * mpcq_sim_control_periods; mpcq_solve is not a period.  On the stream of a period the order is: recorder snapshot -> black-box
+ * snapshot -> ordering launch -> step -> recorder row -> black box -> score -> exploration -> plant -> mission, so the score reads what a recorded row shows: the measurement x the step solved
  * from, the cursor i the step used, ref = row 0 of the reference chunk the step used (MPCQ_RECORD_X_REF), status, qp_iter, cost and the
  * finished flag after the step.  Scoring changes no result of the engine, and with no score running every launch sequence is what it was.
  *
@@ -616,7 +680,7 @@ typedef struct mpcq_plant {              /* one quadrotor's Quadrotor3D; g stays
 /* The fleet period p counts the plant updates the engine has made since period0 was set: one per control period of mpcq_sim_steps /
  * mpcq_sim_control_periods (the same p for every group of that period, see mpcq_tuning.groups) and one per mpcq_sim_plant_period.
  * mpcq_step / mpcq_step_device_async / mpcq_solve update no plant -- the caller owns it -- and are unaffected.  While a fleet is set every
- * plant update of mpcq_sim_steps is a launch of its own, behind the recorder's row and the score and in front of the mission launch (a
+ * plant update of mpcq_sim_steps is a launch of its own, behind the recorder's row, the black box and the score and in front of the mission launch (a
  * mission plans from the fleet plant's state).  mpcq_sim_run (one persistent launch with the shared plant fused in) flies no fleet:
  * MPCQ_ERR_STATE while one is set.  mpcq_reset keeps the table and the period, mpcq_destroy frees it.
  *
@@ -646,7 +710,7 @@ int mpcq_fleet_stop(mpcq_engine* e);
  * a_max of that leg into the mission's legs table before the mission launch of the same period plans it.  Kind and radius stay: a
  * circle leg flies its radius at the explored speed.  leg_limits [B,L,3] logs (explored, v_max, a_max) of every leg written so; NaN
  * where none was (not consumed yet, or not explored).
- *   Launch.  One launch per period and range of quadrotors, behind the step (and the recorder's row and the score), in front of the
+ *   Launch.  One launch per period and range of quadrotors, behind the step (and the recorder's row, the black box and the score), in front of the
  * plant and mission launches, on every period a mission runs on: mpcq_sim_steps (each group's range on its stream),
  * mpcq_sim_control_periods, mpcq_step, mpcq_step_device_async.  mpcq_sim_run: MPCQ_ERR_STATE, as for the mission.  With no exploration
  * started every launch sequence and result is what it was.

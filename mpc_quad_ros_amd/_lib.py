@@ -150,6 +150,13 @@ SYMBOLS = [
     ("mpcq_explore_start", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _dp, _lp]),
     ("mpcq_explore_get", ctypes.c_int, [_vp, _dp, _lp, _dp]),
     ("mpcq_explore_stop", ctypes.c_int, [_vp]),
+    ("mpcq_blackbox_start", ctypes.c_int, [_vp, _ip, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
+    ("mpcq_blackbox_info", ctypes.c_int, [_vp, _lp, _ip, _ip, _ip, _ip, _lp]),
+    ("mpcq_blackbox_get", ctypes.c_int, [_vp, ctypes.c_int32, _ip, ctypes.c_int32, _dp]),
+    ("mpcq_blackbox_get_solver", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _ip]),
+    ("mpcq_blackbox_get_periods", ctypes.c_int, [_vp, _ip, ctypes.c_int32, _lp]),
+    ("mpcq_blackbox_rearm", ctypes.c_int, [_vp, _ip]),
+    ("mpcq_blackbox_stop", ctypes.c_int, [_vp]),
     ("mpcq_learn_last_error", ctypes.c_char_p, []),
     ("mpcq_learn_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _dp, _dp, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mpcq_learn_destroy", ctypes.c_int, [_vp]),

@@ -26,6 +26,7 @@
 #include "mpcq_replan_nl.hpp"
 #include "mpcq_mission.hpp"
 #include "mpcq_record.hpp"
+#include "mpcq_blackbox.hpp"
 #include "mpcq_explore.hpp"
 #include "mpcq_score.hpp"
 #include "mpcq_predict.hpp"
@@ -233,7 +234,9 @@ template <typename Buf> static int grow_or_fail(Buf& buf, size_t elems, const st
 // entry points of each stand in the C ABI part below, under the same heading.  What a period's side launches need to know about the period:
 struct Tick {
   int row = -1;          // the recorder's row (-1: the period is not recorded)
-  int mper = -1;         // the mission's period number (-1: no mission)
+  int bslot = -1;        // the black box's ring slot (-1: no black box)
+  long long bper = -1;   // the black box's period number
+  int mper = -1;        // the mission's period number (-1: no mission)
   long long sper = -1;   // the scoreboard's period number (-1: no score running)
   long long fper = -1;   // the fleet period of the plant update (-1: no fleet, or no plant update drawn)
 };
@@ -262,6 +265,29 @@ struct Recorder {
     period_of.push_back(p);
     return rows++;
   }
+};
+
+// ---- incident recorder (mpcq_blackbox_*, mpcq_blackbox.hpp): a ring of the recorder's rows per watched quadrotor and its trigger state on
+// the device; the launches read the RGP state in the engine's precision and are EngineT's (bb_snapshot, bb_write).  The selection is kept
+// sorted, as the recorder's is, and so are the rules and the per-quadrotor state; pos maps the caller's order to it.
+struct BlackBox {
+  bool on = false;
+  int fields = 0, pre = 0, post = 0, D = 0, count = 0;
+  long long periods = 0;                 // periods issued since mpcq_blackbox_start
+  std::vector<int> sorted, pos;          // selection ascending; pos[j] = place of the caller's j-th quadrotor in `sorted`
+  std::vector<int> glo, ghi;             // part of `sorted` inside entry g of mpcq_engine::groups: [glo[g], ghi[g])
+  DevBuf<int> d_sel;                     // sorted selection
+  DevBuf<mpcq_blackbox_rule> d_rules;    // [count], sorted order
+  DevBuf<double> d_f[mpcq::record::NF - 1];   // double fields, [D][count][width]
+  DevBuf<int> d_solver;                  // [D][count][4]
+  DevBuf<double> d_snap;                 // [count][SNAP] (MPCQ_RECORD_DRAG)
+  DevBuf<int> d_int;                     // ints(): state [count] | cause [count] | left [count]
+  DevBuf<long long> d_i64;               // fired_period [count] | first [count]
+  // read-out staging (mpcq_blackbox_get*): grown on demand
+  DevBuf<double> d_stage;                // [n][D][width]
+  DevBuf<int> d_stage_int;               // which [n] | rows [n] | solver rows [n][D][4]; the mask of a rearm [count]
+  DevBuf<long long> d_stage_p0;          // [n]
+  mpcq::blackbox::State state() const { return mpcq::blackbox::State{d_int.p, d_int.p + count, d_int.p + 2 * (size_t)count, d_i64.p, d_i64.p + count}; }
 };
 
 // ---- device missions (mpcq_mission_*, mpcq_mission.hpp): the queue of upcoming flights, the per-quadrotor leg counters and the log of
@@ -430,16 +456,22 @@ struct mpcq_engine : EngineQueues {
   bool have_sim = false;         // mpcq_sim_reset has set the plant state
   ReplanStaging rp;              // mpcq_replan* / mpcq_replace_trajectories
   Recorder rec;                  // mpcq_record_start .. mpcq_record_stop
+  BlackBox bb;                   // mpcq_blackbox_start .. mpcq_blackbox_stop
   Mission ms;                    // mpcq_mission_set .. mpcq_mission_stop
   Score sc;                      // mpcq_score_start .. mpcq_score_stop
   Fleet fl;                      // mpcq_fleet_set .. mpcq_fleet_stop
   Explore ex;                    // mpcq_explore_start .. mpcq_explore_stop (or the end of the mission: end_exploration)
   // The ticket of the period about to be issued, the one place the features' counters advance.  control: a control period (mpcq_step,
-  // mpcq_step_device_async, every period of mpcq_sim_steps) -- the recorder, the mission and the score count it.  plant: a plant update
+  // mpcq_step_device_async, every period of mpcq_sim_steps) -- the recorder, the black box, the mission and the score count it. plant: a plant update
   // (every period of mpcq_sim_steps, mpcq_sim_plant_period) -- the fleet period advances with it, never with a step alone.
   Tick next_tick(bool control, bool plant) {
     Tick t;
-    if (control) t = Tick{rec.next_row(), ms.on ? (int)ms.periods++ : -1, sc.on ? sc.periods++ : -1, -1};
+    if (control) {
+      t.row = rec.next_row();
+      if (bb.on) { t.bper = bb.periods++; t.bslot = (int)(t.bper % bb.D); }
+      if (ms.on) t.mper = (int)ms.periods++;
+      if (sc.on) t.sper = sc.periods++;
+    }
     if (plant && fl.on) t.fper = fl.period++;
     return t;
   }
@@ -581,7 +613,93 @@ template <typename V> int rec_read(mpcq_engine* e, const V* src, int W, V* out) 
       std::memcpy(out + ((size_t)j * r.rows + k) * W, tmp.data() + ((size_t)k * r.count + r.pos[j]) * W, W * sizeof(V));
   return 0;
 }
-// What the five *_stop entry points do with their feature f of e (not_on: the error of a feature that is not on)
+// ---- incident recorder: what the mpcq_blackbox_* entry points share
+// What a quadrotor's ring holds now, from its device state: its first period p0, the number of rows and the row of the firing period
+struct BoxRows { long long p0; int rows, fired_row; };
+BoxRows box_rows(const BlackBox& r, int state, long long fired, long long first) {
+  if (fired < 0) {   // armed: the last D periods since `first`
+    const long long rows = std::max(0LL, std::min((long long)r.D, r.periods - first));
+    return BoxRows{r.periods - rows, (int)rows, -1};
+  }
+  // fired: the incident, from `pre` periods in front of it (older rows the ring still holds are on their way out: the rows behind the
+  // firing period overwrite them) to the last period written
+  const long long last = state == mpcq::blackbox::FROZEN ? fired + r.post : r.periods - 1;
+  const long long p0 = std::max(first, fired - r.pre);
+  return BoxRows{p0, (int)(last - p0 + 1), (int)(fired - p0)};
+}
+// The device state of the selection, behind everything the engine has enqueued (sorted order)
+struct BoxState { std::vector<int> ints; std::vector<long long> i64; };
+int box_state(mpcq_engine* e, BoxState& h) {
+  const BlackBox& r = e->bb;
+  h.ints.resize(3 * (size_t)r.count); h.i64.resize(2 * (size_t)r.count);
+  HIP_TRY(hipMemcpyAsync(h.ints.data(), r.d_int.p, h.ints.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(h.i64.data(), r.d_i64.p, h.i64.size() * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+// The checks of a read-out's subset (`who`: the entry point): which [n] positions in the caller's selection, or NULL for all of it.
+// sel: the places in the sorted selection, in the caller's order.
+int box_subset(const std::string& who, const BlackBox& r, const int32_t* which, int32_t n, std::vector<int>& sel) {
+  if (which && n < 0) return fail(MPCQ_ERR_INVALID, who + ": n must be >= 0");
+  const int m = which ? n : r.count;
+  sel.resize(m);
+  std::vector<char> seen(r.count, 0);
+  for (int i = 0; i < m; ++i) {
+    const int j = which ? which[i] : i;
+    if (j < 0 || j >= r.count) return fail(MPCQ_ERR_INVALID, who + ": position " + std::to_string(j) + " outside the selection [0, " + std::to_string(r.count) + ")");
+    if (seen[j]++) return fail(MPCQ_ERR_INVALID, who + ": duplicate position " + std::to_string(j));
+    sel[i] = r.pos[j];
+  }
+  return 0;
+}
+// One field's rings of the subset in time order: src [D][count][W] on the device -> out [n][D][W] on the host, through the staging block
+template <typename V> int box_read(mpcq_engine* e, const std::string& who, const V* src, int W, V fill, const int32_t* which, int32_t n, V* out) {
+  namespace bx = mpcq::blackbox;
+  BlackBox& r = e->bb;
+  std::vector<int> sel;
+  if (const int rc = box_subset(who, r, which, n, sel)) return rc;
+  const size_t m = sel.size(), total = m * r.D * W;
+  if (!total) return 0;
+  if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
+  if ((total + 63) / 64 > 0x7fffffffull) return fail(MPCQ_ERR_INVALID, who + ": too many values for one call (n x D x width): read a subset");
+  BoxState h;
+  if (const int rc = box_state(e, h)) return rc;
+  std::vector<int> meta(2 * m);   // which | rows
+  std::vector<long long> p0(m);
+  for (size_t i = 0; i < m; ++i) {
+    const int j = sel[i];
+    const BoxRows br = box_rows(r, h.ints[j], h.i64[j], h.i64[r.count + j]);
+    meta[i] = j; meta[m + i] = br.rows; p0[i] = br.p0;
+  }
+  const bool ints = sizeof(V) == sizeof(int);
+  const std::string no_mem = who + ": cannot allocate the staging block of " + std::to_string(total * sizeof(V)) + " bytes";
+  int rc;
+  if ((rc = grow_or_fail(r.d_stage_int, 2 * m + (ints ? total : 0), no_mem)) || (rc = grow_or_fail(r.d_stage_p0, m, no_mem))) return rc;
+  if (!ints && (rc = grow_or_fail(r.d_stage, total, no_mem))) return rc;
+  V* d_out = ints ? (V*)(r.d_stage_int.p + 2 * m) : (V*)r.d_stage.p;
+  HIP_TRY(hipMemcpyAsync(r.d_stage_int.p, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(r.d_stage_p0.p, p0.data(), m * sizeof(long long), hipMemcpyHostToDevice, e->stream));
+  const int *d_which = r.d_stage_int.p, *d_rows = r.d_stage_int.p + m;
+  const long long* d_p0 = r.d_stage_p0.p;
+  const int D = r.D, count = r.count;
+  hipStream_t s = e->stream;
+  hipLaunchKernelGGL(bx::gather_kernel<V>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, src, d_which, d_p0, d_rows, (long)total, D, W, count, fill, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, d_out, total * sizeof(V), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+// The state of the selected places (d_mask [count] in sorted order on the device, or nullptr: all) to armed, the ring beginning with `first`
+int box_init(mpcq_engine* e, const int* d_mask, long long first) {
+  const mpcq::blackbox::State st = e->bb.state();
+  const int count = e->bb.count;
+  hipStream_t s = e->stream;
+  hipLaunchKernelGGL(mpcq::blackbox::init_kernel, dim3((count + 63) / 64), dim3(64), 0, s, st, d_mask, count, first);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+// What the six *_stop entry points do with their feature f of e (not_on: the error of a feature that is not on)
 template <typename F> int feature_stop(mpcq_engine* e, F& f, const char* not_on) {
   if (!f.on) return fail(MPCQ_ERR_STATE, not_on);
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the feature's buffers)
@@ -953,20 +1071,52 @@ struct EngineT : mpcq_engine {
     if (n <= 0) return;
     mpcq::record::Args<T> a;
     std::memset(&a, 0, sizeof(a));
-    a.sel = rec.d_sel.p; a.j0 = j0; a.n = n; a.count = rec.count; a.row = row;
+    const long blocks = row_args(a, rec, j0, n, row, xmeas);
+    hipLaunchKernelGGL(mpcq::record::record_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+  }
+  // The arguments of a row launch of the recorder or the black box (r: either; both keep fields, count, d_sel, d_f, d_solver, d_snap) for
+  // the selection part [j0, j0 + n) and write position `row`; returns the blocks of the launch.
+  template <typename R> long row_args(mpcq::record::Args<T>& a, const R& r, int j0, int n, int row, const double* xmeas) {
+    a.sel = r.d_sel.p; a.j0 = j0; a.n = n; a.count = r.count; a.row = row;
     long blocks = 0;
     for (int f = 0; f < mpcq::record::NF; ++f) {
       a.blk[f] = (int)blocks;
-      if (rec.fields >> f & 1) blocks += ((long)n * mpcq::record::width(f, nb) + 63) / 64;
+      if (r.fields >> f & 1) blocks += ((long)n * mpcq::record::width(f, nb) + 63) / 64;
     }
     a.blk[mpcq::record::NF] = (int)blocks;
-    for (int f = 0; f < mpcq::record::NF - 1; ++f) a.out[f] = rec.d_f[f].p;
-    a.solver = rec.d_solver.p; a.snap = rec.d_snap.p;
+    for (int f = 0; f < mpcq::record::NF - 1; ++f) a.out[f] = r.d_f[f].p;
+    a.solver = r.d_solver.p; a.snap = r.d_snap.p;
     a.xmeas = xmeas; a.w = st.w; a.xpred = st.xpred; a.cost = st.cost; a.traj = st.traj;
     a.tlen = st.tlen; a.idx = st.idx; a.finished = st.finished; a.status = st.status; a.qp_iter = st.qp_iter;
     a.mu = st.mu; a.C = st.C;
     a.Tmax = m.Tmax; a.N = N; a.skip = m.skip; a.nb = nb; a.dt_pred = m.dt_pred;
-    hipLaunchKernelGGL(mpcq::record::record_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+    return blocks;
+  }
+  // ---- incident recorder (mpcq_blackbox.hpp), selection part [j0, j1).  In front of the step launch, behind the recorder's snapshot: the
+  // black box's own snapshot
+  void bb_snapshot(hipStream_t s, int j0, int j1) {
+    const int n = j1 - j0;
+    if (!(bb.fields & MPCQ_RECORD_DRAG) || n <= 0) return;
+    hipLaunchKernelGGL(mpcq::record::record_snapshot_kernel, dim3((n * mpcq::record::SNAP + 63) / 64), dim3(64), 0, s, (const int*)bb.d_sel.p, j0, n,
+                       (const double*)st.xpp, (const int*)st.has_prev, bb.d_snap.p);
+  }
+  // behind the recorder's row, in front of the score: period `per` into ring slot `slot` of whoever is not frozen, then the judge
+  void bb_write(hipStream_t s, int j0, int j1, int slot, long long per, const double* xmeas) {
+    namespace bx = mpcq::blackbox;
+    const int n = j1 - j0;
+    if (n <= 0) return;
+    bx::RowArgs<T> a;
+    std::memset(&a, 0, sizeof(a));
+    const long blocks = row_args(a, bb, j0, n, slot, xmeas);
+    a.state = bb.state().state;
+    hipLaunchKernelGGL(bx::row_kernel<T>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+    bx::JudgeArgs g;
+    g.sel = bb.d_sel.p; g.j0 = j0; g.n = n; g.rules = bb.d_rules.p; g.st = bb.state();
+    g.period = per; g.post = bb.post;
+    g.xmeas = xmeas; g.w = st.w; g.cost = st.cost; g.traj = st.traj;
+    g.tlen = st.tlen; g.idx = st.idx; g.status = st.status; g.qp_iter = st.qp_iter;
+    g.Tmax = m.Tmax; g.N = N; g.skip = m.skip;
+    hipLaunchKernelGGL(bx::judge_kernel, dim3((n + 63) / 64), dim3(64), 0, s, g);
   }
   // The plant update of the quadrotors [b0, b0 + n): n_sub substeps of sim_dt on xs [B,13] with the controls st.w.  The engine's shared plant
   // (plant_kernel, which reads the model in the engine's precision), or with a fleet set (fper >= 0: its fleet period) every quadrotor's own
@@ -990,8 +1140,9 @@ struct EngineT : mpcq_engine {
   // The optional events of a period (see period)
   struct PeriodEvents { hipEvent_t front = nullptr, step = nullptr, end = nullptr; };
   // One period of groups[gi], the only place that issues one.  On the group's stream, in this order:
-  //   the recorder's snapshot (t.row >= 0: the period is recorded) -> ev.front -> ordering launch -> ev.step -> step kernel -> ev.end
-  //   -> the recorder's row -> the scoreboard's launch (t.sper >= 0) -> the exploration launch (an exploration runs and t.mper >= 0)
+  //   the recorder's snapshot (t.row >= 0: the period is recorded) -> the black box's snapshot (t.bslot >= 0: a black box runs) -> ev.front
+  //   -> ordering launch -> ev.step -> step kernel -> ev.end -> the recorder's row -> the black box's row and judge launches
+  //   -> the scoreboard's launch (t.sper >= 0) -> the exploration launch (an exploration runs and t.mper >= 0)
   //   -> the plant update (plant: s.run_nsub substeps of s.run_dt on s.run_x; with t.fper >= 0 the fleet's launch, plant_launch)
   //   -> the mission launch (t.mper >= 0; the flights start at the plant state behind its update, or without a plant at the period's
   //   measurement).
@@ -1001,10 +1152,12 @@ struct EngineT : mpcq_engine {
     if (g.n <= 0) return 0;
     const EngineView v = view();
     if (t.row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
+    if (t.bslot >= 0) bb_snapshot(g.stream, bb.glo[gi], bb.ghi[gi]);
     if (ev.front) HIP_TRY(hipEventRecord(ev.front, g.stream));
     launch_period(s, mode, ev.step, g.stream, g.b0, g.n);
     if (ev.end) HIP_TRY(hipEventRecord(ev.end, g.stream));
     if (t.row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], t.row, s.x_meas);
+    if (t.bslot >= 0) bb_write(g.stream, bb.glo[gi], bb.ghi[gi], t.bslot, t.bper, s.x_meas);
     if (t.sper >= 0) score_launch(sc, v, B, g.stream, g.b0, g.n, t.sper, s.x_meas);
     if (ex.on && t.mper >= 0) explore_launch(ex, ms, v, B, g.stream, g.b0, g.n, s.x_meas);
     if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, t.fper);
@@ -1154,6 +1307,7 @@ struct EngineT : mpcq_engine {
   int sim_run(int K, int n_sub, double sim_dt) override {
     if (const int rc = needs_trajectories(this, "mpcq_sim_run")) return rc;
     if (rec.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot record (one persistent launch): mpcq_record_stop first, or use mpcq_sim_steps");
+    if (bb.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot keep a black box (one persistent launch): mpcq_blackbox_stop first, or use mpcq_sim_steps");
     if (ex.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot explore (one persistent launch): mpcq_explore_stop and mpcq_mission_stop first, or use mpcq_sim_steps");
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
     if (sc.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot score flights (one persistent launch): mpcq_score_stop first, or use mpcq_sim_steps");
@@ -1908,6 +2062,149 @@ int mpcq_record_clear(mpcq_engine* e) {
   return 0;
 }
 int mpcq_record_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->rec, "mpcq_record_stop: no active recording"); }
+
+// ---- incident recorder (mpcq_blackbox.hpp; state: BlackBox; the launches: EngineT::bb_snapshot / bb_write)
+int mpcq_blackbox_start(mpcq_engine* e, const int32_t* quads, int32_t count, int32_t fields, int32_t pre, int32_t post, const mpcq_blackbox_rule* rules) {
+  ENTER(e);
+  namespace bx = mpcq::blackbox;
+  const std::string who("mpcq_blackbox_start");
+  if (e->bb.on) return fail(MPCQ_ERR_STATE, who + ": a black box is running (mpcq_blackbox_stop first)");
+  if (quads && count <= 0) return fail(MPCQ_ERR_INVALID, who + ": count must be > 0");
+  if (fields == 0 || (fields & ~MPCQ_RECORD_ALL)) return fail(MPCQ_ERR_INVALID, who + ": fields empty or unknown bits");
+  if (!e->nb && (fields & (MPCQ_RECORD_RGP_MU | MPCQ_RECORD_RGP_C))) return fail(MPCQ_ERR_INVALID, who + ": RGP fields on an engine with nb = 0");
+  if (pre < 0 || post < 0) return fail(MPCQ_ERR_INVALID, who + ": pre and post must be >= 0");
+  if ((long long)pre + 1 + post > 65536) return fail(MPCQ_ERR_INVALID, who + ": ring depth pre + 1 + post must be <= 65536");
+  if (!rules) return fail(MPCQ_ERR_INVALID, who + ": rules is NULL");
+  const int n = quads ? count : e->B;
+  std::vector<int> sel(n);
+  std::vector<char> seen(e->B, 0);
+  for (int j = 0; j < n; ++j) {
+    sel[j] = quads ? quads[j] : j;
+    if (sel[j] < 0 || sel[j] >= e->B) return fail(MPCQ_ERR_INVALID, who + ": quadrotor index out of range");
+    if (seen[sel[j]]++) return fail(MPCQ_ERR_INVALID, who + ": duplicate quadrotor index");
+  }
+  // every rule is checked before anything is allocated
+  for (int j = 0; j < n; ++j) {
+    const mpcq_blackbox_rule& r = rules[j];
+    auto bad = [&](const char* field, const char* rule) { return fail(MPCQ_ERR_INVALID, who + ": quadrotor " + std::to_string(sel[j]) + ": " + field + " " + rule); };
+    if (r.causes & ~bx::C_ALL) return bad("causes", "has unknown bits");
+    const struct { const char* name; double v; int cause; } th[] = {{"err_pos", r.err_pos, MPCQ_BB_ERR_POS}, {"speed", r.speed, MPCQ_BB_SPEED},
+                                                                    {"tilt_cos", r.tilt_cos, MPCQ_BB_TILT}, {"cost", r.cost, MPCQ_BB_COST}};
+    for (const auto& t : th)
+      if ((r.causes & t.cause) && std::isnan(t.v)) return bad(t.name, "is NaN and its cause is enabled");
+    if (r.err_pos < 0) return bad("err_pos", "must be >= 0");
+    if (r.speed < 0) return bad("speed", "must be >= 0");
+  }
+  BlackBox nr;
+  nr.fields = fields; nr.pre = pre; nr.post = post; nr.D = pre + 1 + post; nr.count = n;
+  nr.sorted = sel;
+  std::sort(nr.sorted.begin(), nr.sorted.end());
+  nr.pos.resize(n);
+  std::vector<mpcq_blackbox_rule> sorted_rules(n);
+  for (int j = 0; j < n; ++j) {
+    nr.pos[j] = (int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), sel[j]) - nr.sorted.begin());
+    sorted_rules[nr.pos[j]] = rules[j];
+  }
+  for (const Group& g : e->groups) {   // the part of the selection inside every group of mpcq_sim_steps, and inside the whole batch
+    nr.glo.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g.b0) - nr.sorted.begin()));
+    nr.ghi.push_back((int)(std::lower_bound(nr.sorted.begin(), nr.sorted.end(), g.b0 + g.n) - nr.sorted.begin()));
+  }
+  // (a return from here on releases what `nr` holds by then; the engine's black box is touched by the last statements only)
+  auto need = [&](auto& buf, size_t elems, const char* what) {
+    return grow_or_fail(buf, elems, who + ": cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes for " + what);
+  };
+  int rc = need(nr.d_sel, (size_t)n, "the selection");
+  if (!rc) rc = need(nr.d_rules, (size_t)n, "the rules");
+  if (!rc) rc = need(nr.d_int, 3 * (size_t)n, "the state");
+  if (!rc) rc = need(nr.d_i64, 2 * (size_t)n, "the state");
+  for (int f = 0; f < mpcq::record::NF && !rc; ++f) {
+    if (!(fields >> f & 1)) continue;
+    const size_t elems = (size_t)nr.D * n * mpcq::record::width(f, e->nb);
+    rc = f == mpcq::record::F_SOLVER ? need(nr.d_solver, elems, "the solver field") : need(nr.d_f[f], elems, "a field's rings");
+  }
+  if (!rc && (fields & MPCQ_RECORD_DRAG)) rc = need(nr.d_snap, (size_t)n * mpcq::record::SNAP, "the drag snapshot");
+  if (rc) return rc;
+  if (hipMemcpyAsync(nr.d_sel.p, nr.sorted.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+      hipMemcpyAsync(nr.d_rules.p, sorted_rules.data(), (size_t)n * sizeof(mpcq_blackbox_rule), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    return fail(MPCQ_ERR_DEVICE, who + ": copy of the selection and the rules failed");
+  const bx::State st0 = nr.state();
+  hipStream_t s = e->stream;
+  hipLaunchKernelGGL(bx::init_kernel, dim3((n + 63) / 64), dim3(64), 0, s, st0, (const int*)nullptr, n, 0LL);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return fail(MPCQ_ERR_DEVICE, who + ": the state could not be set");
+  nr.on = true;
+  e->bb = std::move(nr);
+  return 0;
+}
+int mpcq_blackbox_info(mpcq_engine* e, int64_t* fired_period, int32_t* cause, int32_t* state, int32_t* rows, int32_t* fired_row, int64_t* periods) {
+  ENTER(e);
+  const BlackBox& r = e->bb;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_blackbox_info: no black box running");
+  if (periods) *periods = r.periods;
+  if (!fired_period && !cause && !state && !rows && !fired_row) return 0;
+  BoxState h;
+  if (const int rc = box_state(e, h)) return rc;
+  const size_t n = r.count;
+  for (size_t j = 0; j < n; ++j) {   // caller's order
+    const size_t k = r.pos[j];
+    const BoxRows br = box_rows(r, h.ints[k], h.i64[k], h.i64[n + k]);
+    if (fired_period) fired_period[j] = h.i64[k];
+    if (cause) cause[j] = h.ints[n + k];
+    if (state) state[j] = h.ints[k];
+    if (rows) rows[j] = br.rows;
+    if (fired_row) fired_row[j] = br.fired_row;
+  }
+  return 0;
+}
+int mpcq_blackbox_get(mpcq_engine* e, int32_t field, const int32_t* which, int32_t n, double* out) {
+  ENTER(e);
+  const BlackBox& r = e->bb;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_blackbox_get: no black box running");
+  if (field <= 0 || (field & (field - 1)) || !(field & r.fields) || field == MPCQ_RECORD_SOLVER)
+    return fail(MPCQ_ERR_INVALID, "mpcq_blackbox_get: field is not one double field of this black box (MPCQ_RECORD_SOLVER: mpcq_blackbox_get_solver)");
+  int f = 0;
+  while (!(field >> f & 1)) ++f;
+  return box_read(e, "mpcq_blackbox_get", (const double*)r.d_f[f].p, mpcq::record::width(f, e->nb), std::nan(""), which, n, out);
+}
+int mpcq_blackbox_get_solver(mpcq_engine* e, const int32_t* which, int32_t n, int32_t* out) {
+  ENTER(e);
+  const BlackBox& r = e->bb;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_blackbox_get_solver: no black box running");
+  if (!(r.fields & MPCQ_RECORD_SOLVER)) return fail(MPCQ_ERR_INVALID, "mpcq_blackbox_get_solver: MPCQ_RECORD_SOLVER is not a field of this black box");
+  return box_read(e, "mpcq_blackbox_get_solver", (const int*)r.d_solver.p, 4, -1, which, n, (int*)out);
+}
+int mpcq_blackbox_get_periods(mpcq_engine* e, const int32_t* which, int32_t n, int64_t* out) {
+  ENTER(e);
+  const BlackBox& r = e->bb;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_blackbox_get_periods: no black box running");
+  std::vector<int> sel;
+  if (const int rc = box_subset("mpcq_blackbox_get_periods", r, which, n, sel)) return rc;
+  if (sel.empty()) return 0;
+  if (!out) return fail(MPCQ_ERR_INVALID, "null argument");
+  BoxState h;
+  if (const int rc = box_state(e, h)) return rc;
+  for (size_t i = 0; i < sel.size(); ++i) {
+    const int j = sel[i];
+    const BoxRows br = box_rows(r, h.ints[j], h.i64[j], h.i64[r.count + j]);
+    for (int k = 0; k < r.D; ++k) out[i * r.D + k] = k < br.rows ? br.p0 + k : -1;
+  }
+  return 0;
+}
+int mpcq_blackbox_rearm(mpcq_engine* e, const int32_t* mask) {
+  ENTER(e);
+  BlackBox& r = e->bb;
+  if (!r.on) return fail(MPCQ_ERR_STATE, "mpcq_blackbox_rearm: no black box running");
+  const int* d_mask = nullptr;
+  if (mask) {
+    std::vector<int> m(r.count);
+    for (int j = 0; j < r.count; ++j) m[r.pos[j]] = mask[j] != 0;
+    if (const int rc = grow_or_fail(r.d_stage_int, (size_t)r.count, "mpcq_blackbox_rearm: cannot allocate the mask")) return rc;
+    HIP_TRY(hipMemcpyAsync(r.d_stage_int.p, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (m leaves scope)
+    d_mask = r.d_stage_int.p;
+  }
+  return box_init(e, d_mask, r.periods);
+}
+int mpcq_blackbox_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->bb, "mpcq_blackbox_stop: no black box running"); }
 
 // ---- flight scoreboard (mpcq_score.hpp; state, layout and launch: Score, score_launch)
 namespace {

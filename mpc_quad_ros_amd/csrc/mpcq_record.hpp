@@ -43,8 +43,18 @@ __device__ inline double v_body_axis(const double* x, int i) {
   return r0 * x[7] + r1 * x[8] + r2 * x[9];
 }
 
+// What a row is read from: the device state a step left (and, for MPCQ_RECORD_DRAG, the snapshot taken in front of it)
 template <typename TQ>
-struct Args {
+struct Source {
+  const double* snap;  // [count][SNAP]
+  const double* xmeas; const double* w; const double* xpred; const double* cost; const double* traj;
+  const int* tlen; const int* idx; const int* finished; const int* status; const int* qp_iter;
+  const TQ* mu; const TQ* C;
+  int Tmax, N, skip, nb;
+  double dt_pred;
+};
+template <typename TQ>
+struct Args : Source<TQ> {
   const int* sel;      // selection, sorted [count]
   int j0, n;           // the part of the selection this launch covers: [j0, j0 + n)
   int count;           // selection size (row stride of a slab)
@@ -52,12 +62,6 @@ struct Args {
   int blk[NF + 1];     // first block of each field; blk[NF] = blocks of the launch (a field not recorded has no blocks)
   double* out[NF - 1]; // double fields [capacity][count][width]
   int* solver;         // [capacity][count][4] int32
-  const double* snap;  // [count][SNAP]
-  const double* xmeas; const double* w; const double* xpred; const double* cost; const double* traj;
-  const int* tlen; const int* idx; const int* finished; const int* status; const int* qp_iter;
-  const TQ* mu; const TQ* C;
-  int Tmax, N, skip, nb;
-  double dt_pred;
 };
 
 __global__ void __launch_bounds__(64) record_snapshot_kernel(const int* sel, int j0, int n, const double* xpp, const int* has_prev, double* snap) {
@@ -67,29 +71,20 @@ __global__ void __launch_bounds__(64) record_snapshot_kernel(const int* sel, int
   snap[(size_t)j * SNAP + k] = k < NX ? xpp[(size_t)b * NX + k] : (double)has_prev[b];
 }
 
+// Element e of double field f (not F_SOLVER) of the period the step has just left, for quadrotor b at place j of the selection.  The one
+// place a row value is made: record_kernel and the black box's row kernel (mpcq_blackbox.hpp) both store what this returns.
 template <typename TQ>
-__global__ void __launch_bounds__(64) record_kernel(const Args<TQ> a) {
-  const int bx = blockIdx.x;
-  int f = 0, first = 0;   // the field of this block (block-uniform; constant indices keep the argument arrays out of scratch)
-#pragma unroll
-  for (int k = 1; k < NF; ++k)
-    if (bx >= a.blk[k]) { f = k; first = a.blk[k]; }
-  const int W = width(f, a.nb);
-  const long t = (long)(bx - first) * 64 + threadIdx.x;
-  if (t >= (long)a.n * W) return;
-  const int jl = (int)(t / W), e = (int)(t - (long)jl * W), j = a.j0 + jl, b = a.sel[j];
-  const size_t o = ((size_t)a.row * a.count + j) * W + e;
+__device__ inline double row_value(const Source<TQ>& a, int f, int e, int j, int b) {
   switch (f) {
-    case F_XODOM: a.out[F_XODOM][o] = a.xmeas[(size_t)b * NX + e]; break;
+    case F_XODOM: return a.xmeas[(size_t)b * NX + e];
     case F_XREF: {   // row 0 of the chunk the step used: the post phase has advanced the cursor by one
       const int idx = a.idx[b] - 1, len = a.tlen[b];
       const long r = chunk_row(0, chunk_have(len, idx, a.N, a.skip), idx, a.skip, len);
-      a.out[F_XREF][o] = a.traj[((size_t)b * a.Tmax + r) * NX + e];
-      break;
+      return a.traj[((size_t)b * a.Tmax + r) * NX + e];
     }
-    case F_W: a.out[F_W][o] = a.w[(size_t)b * NU + e]; break;
-    case F_XPRED: a.out[F_XPRED][o] = a.xpred[(size_t)b * NX + e]; break;
-    case F_COST: a.out[F_COST][o] = a.cost[b]; break;
+    case F_W: return a.w[(size_t)b * NU + e];
+    case F_XPRED: return a.xpred[(size_t)b * NX + e];
+    case F_COST: return a.cost[b];
     case F_DRAG: {   // compute_a_drag of the post phase (mpcq_kernels.hpp, step_kernel section 4) against the snapshot
       double x[NX], xq[NX];
       const double* sn = a.snap + (size_t)j * SNAP;
@@ -98,20 +93,52 @@ __global__ void __launch_bounds__(64) record_kernel(const Args<TQ> a) {
       for (int k = 0; k < NX; ++k) { x[k] = a.xmeas[(size_t)b * NX + k]; xq[k] = hp ? sn[k] : x[k]; }
       const int c = e < 3 ? e : e - 3;
       const double vb = v_body_axis(x, c), vp = v_body_axis(xq, c);
-      a.out[F_DRAG][o] = e < 3 ? vb : (vb - vp) / a.dt_pred;
-      break;
+      return e < 3 ? vb : (vb - vp) / a.dt_pred;
     }
-    case F_MU: a.out[F_MU][o] = (double)a.mu[(size_t)b * 3 * a.nb + e]; break;
-    case F_C: a.out[F_C][o] = (double)a.C[(size_t)b * 3 * a.nb * a.nb + e]; break;
-    default: {
-      int v;
-      if (e == 0) v = a.status[b];
-      else if (e == 1) v = a.qp_iter[b];
-      else if (e == 2) v = a.idx[b] - 1;
-      else v = a.finished[b];
-      a.solver[o] = v;
-    }
+    case F_MU: return (double)a.mu[(size_t)b * 3 * a.nb + e];
+    default: return (double)a.C[(size_t)b * 3 * a.nb * a.nb + e];
   }
+}
+// Element e of F_SOLVER: status, qp_iter, the cursor the step used, the finished flag after the step
+template <typename TQ>
+__device__ inline int solver_value(const Source<TQ>& a, int e, int b) {
+  if (e == 0) return a.status[b];
+  if (e == 1) return a.qp_iter[b];
+  if (e == 2) return a.idx[b] - 1;
+  return a.finished[b];
+}
+// The lane's place in a launch over a.blk: field f, element e, place j of the selection.  false: the lane is beyond its field's slab.
+template <typename TQ>
+__device__ inline bool lane_place(const Args<TQ>& a, int bx, int lane, int& f, int& e, int& j) {
+  int first = 0;   // the field of this block (block-uniform; constant indices keep the argument arrays out of scratch)
+  f = 0;
+#pragma unroll
+  for (int k = 1; k < NF; ++k)
+    if (bx >= a.blk[k]) { f = k; first = a.blk[k]; }
+  const int W = width(f, a.nb);
+  const long t = (long)(bx - first) * 64 + lane;
+  if (t >= (long)a.n * W) return false;
+  const int jl = (int)(t / W);
+  e = (int)(t - (long)jl * W); j = a.j0 + jl;
+  return true;
+}
+// The lane's value into row a.row of its field's slab
+template <typename TQ>
+__device__ inline void put_row(const Args<TQ>& a, int f, int e, int j) {
+  const int b = a.sel[j];
+  const size_t o = ((size_t)a.row * a.count + j) * width(f, a.nb) + e;
+  if (f == F_SOLVER) { a.solver[o] = solver_value(a, e, b); return; }
+  double* dst = a.out[0];
+#pragma unroll
+  for (int k = 1; k < NF - 1; ++k)
+    if (f == k) dst = a.out[k];
+  dst[o] = row_value(a, f, e, j, b);
+}
+
+template <typename TQ>
+__global__ void __launch_bounds__(64) record_kernel(const Args<TQ> a) {
+  int f, e, j;
+  if (lane_place(a, (int)blockIdx.x, (int)threadIdx.x, f, e, j)) put_row(a, f, e, j);
 }
 
 }  // namespace record

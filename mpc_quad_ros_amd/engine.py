@@ -315,6 +315,109 @@ class Engine:
         self._check(self.lib.mpcq_record_stop(self.h))
         self._rec = None
 
+    # ---- incident recorder: a ring of the recorder's rows per watched quadrotor, stopped on the device by a rule of its own
+    def blackbox_start(self, rules, quads=None, fields=RECORD_DEFAULT, pre=50, post=20):
+        """Watch quadrotors `quads` (None: all, else indices in the order the read-outs return them) from the next period on: each keeps
+        the last pre + 1 + post rows of the fields named (RECORD_FIELDS, as record_start takes them) in a ring on the device, and the ring
+        stops `post` periods after the quadrotor's rule first fires.  rules: [count] of params.BLACKBOX_RULE_DTYPE in the order of
+        `quads` (params.blackbox_rules builds them)."""
+        from .params import BLACKBOX_RULE_DTYPE
+        if fields is RECORD_DEFAULT and not self.nb:
+            fields = tuple(f for f in fields if not f.startswith("rgp"))
+        unknown = set(fields) - set(RECORD_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown record fields {sorted(unknown)}")
+        mask = 0
+        for f in fields:
+            mask |= RECORD_FIELDS[f]
+        q = None if quads is None else np.ascontiguousarray(quads, dtype=np.int32).reshape(-1)
+        count = self.B if q is None else len(q)
+        rules = np.ascontiguousarray(rules)
+        if rules.dtype != BLACKBOX_RULE_DTYPE or rules.shape != (count,):
+            raise ValueError(f"rules must be a [count={count}] array of params.BLACKBOX_RULE_DTYPE")
+        self._check(self.lib.mpcq_blackbox_start(self.h, _lib.i(q), 0 if q is None else len(q), mask, int(pre), int(post), rules.ctypes.data))
+        self._bb = dict(quads=np.arange(self.B, dtype=np.int32) if q is None else q.copy(), fields=mask, D=int(pre) + 1 + int(post))
+
+    def _bb_state(self):
+        bb = getattr(self, "_bb", None)
+        if bb is None:
+            raise _lib.MpcqError("no black box running (blackbox_start first)")
+        return bb
+
+    def blackbox_info(self):
+        """The state of every watched quadrotor, in the order of blackbox_start: fired_period [count] (-1: not fired), cause (BB_* bits
+        of the firing period), state (0 armed, 1 fired, 2 frozen), rows (valid rows of the ring), fired_row (index of the firing row in the
+        read-out, -1), and periods (counted since blackbox_start), quads."""
+        bb = self._bb_state()
+        n = len(bb["quads"])
+        out = dict(fired_period=np.zeros(n, np.int64), cause=np.zeros(n, np.int32), state=np.zeros(n, np.int32), rows=np.zeros(n, np.int32),
+                   fired_row=np.zeros(n, np.int32))
+        periods = ctypes.c_int64()
+        self._check(self.lib.mpcq_blackbox_info(self.h, _lib.l(out["fired_period"]), _lib.i(out["cause"]), _lib.i(out["state"]), _lib.i(out["rows"]),
+                                                _lib.i(out["fired_row"]), ctypes.byref(periods)))
+        out["periods"], out["quads"] = periods.value, bb["quads"].copy()
+        return out
+
+    def blackbox_get(self, which=None):
+        """The rings of a subset of the watched quadrotors, gathered on the device in time order and left-aligned: which = None (all),
+        "fired" (those whose rule has fired) or positions in the selection of blackbox_start.  Keys as record_get's with shape
+        [n, D, ...] (rows beyond rows[i] NaN, -1 for status, qp_iter, idx, finished), period [n, D] (-1 beyond rows), and rows,
+        fired_row, fired_period, cause, state, quads [n], which [n] (the positions read)."""
+        bb = self._bb_state()
+        info = self.blackbox_info()
+        if which is None:
+            w = np.arange(len(bb["quads"]), dtype=np.int32)
+        elif isinstance(which, str):
+            if which != "fired":
+                raise ValueError('which must be None, "fired" or positions in the selection')
+            w = np.flatnonzero(info["fired_period"] >= 0).astype(np.int32)
+        else:
+            w = np.ascontiguousarray(which, dtype=np.int32).reshape(-1)
+        n, D, nb, mask = len(w), bb["D"], self.nb, bb["fields"]
+        out = dict(which=w.copy(), period=np.full((n, D), -1, np.int64))
+        self._check(self.lib.mpcq_blackbox_get_periods(self.h, _lib.i(w), n, _lib.l(out["period"])))
+        for k in ("rows", "fired_row", "fired_period", "cause", "state", "quads"):
+            out[k] = info[k][w].copy()
+
+        def get(bit, width):
+            a = np.zeros((n, D, width))
+            self._check(self.lib.mpcq_blackbox_get(self.h, bit, _lib.i(w), n, _lib.d(a)))
+            return a
+        for name, bit, shape in (("x_odom", 1, (NX,)), ("x_ref", 2, (NX,)), ("w_odom", 4, (NU,)), ("x_pred_odom", 8, (NX,)),
+                                 ("cost_solution", 16, ()), ("rgp_mu_g_t", 64, (3, nb)), ("rgp_C_g_t", 128, (3, nb, nb))):
+            if mask & bit:
+                out[name] = get(bit, int(np.prod(shape, dtype=np.int64))).reshape((n, D) + shape)
+        if mask & 32:
+            d = get(32, 6)
+            out["v_body"], out["a_drag"] = d[:, :, 0:3].copy(), d[:, :, 3:6].copy()
+        if mask & 256:
+            sv = np.zeros((n, D, 4), np.int32)
+            self._check(self.lib.mpcq_blackbox_get_solver(self.h, _lib.i(w), n, _lib.i(sv)))
+            for k, name in enumerate(("status", "qp_iter", "idx", "finished")):
+                out[name] = sv[:, :, k].copy()
+        return out
+
+    @staticmethod
+    def blackbox_recording(box, j):
+        """Item j of a blackbox_get() result as a record_get()-shaped dict of its valid rows (count 1, T = rows[j]): what
+        logger.SwarmLogger.from_recording takes, so an incident is written in the reference's pickle layout like any recording."""
+        T = int(box["rows"][j])
+        meta = ("which", "rows", "fired_row", "fired_period", "cause", "state", "quads", "period")
+        out = {k: v[j:j + 1, :T].copy() for k, v in box.items() if k not in meta}
+        out["period"], out["quads"], out["dropped"] = box["period"][j, :T].copy(), box["quads"][j:j + 1].copy(), 0
+        return out
+
+    def blackbox_rearm(self, mask=None):
+        """The selected quadrotors (mask [count] non-zero, in the order of blackbox_start; None: all) back to armed with an empty ring
+        that begins with the next period; the others keep what they hold."""
+        bb = self._bb_state()
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.int32).reshape(len(bb["quads"]))
+        self._check(self.lib.mpcq_blackbox_rearm(self.h, _lib.i(m)))
+
+    def blackbox_stop(self):
+        self._check(self.lib.mpcq_blackbox_stop(self.h))
+        self._bb = None
+
     # ---- flight scoreboard: every period folded on the device into the row of the flight the quadrotor is flying, read once
     def score_start(self, flights, tail_rows=0):
         """Score every flight from the next period on: `flights` slots per quadrotor, a slot opened by every period whose step used

@@ -302,3 +302,87 @@ def explore_velocity(env, samples, rules):
     nxt = explored + rules["step"]
     v = np.where(nxt < rules["desired"], nxt, rules["desired"])
     return explored, np.where(v > rules["v_limit"], rules["v_limit"], v), np.where(v > rules["a_limit"], rules["a_limit"], v)
+
+
+# ---------------------------------------------------------------------------------------------
+# Incident recorder (include/mpcq.h mpcq_blackbox_*): a ring of the flight recorder's rows per watched quadrotor, stopped by a rule of its
+# own that the device judges every period.
+BB_STATUS, BB_FALLBACK, BB_NONFINITE, BB_ERR_POS, BB_SPEED, BB_TILT, BB_COST = 1, 2, 4, 8, 16, 32, 64
+BB_CAUSES = {"status": BB_STATUS, "fallback": BB_FALLBACK, "nonfinite": BB_NONFINITE, "err_pos": BB_ERR_POS, "speed": BB_SPEED,
+             "tilt": BB_TILT, "cost": BB_COST}
+BLACKBOX_RULE_DTYPE = np.dtype([("causes", np.int32), ("status_mask", np.int32), ("err_pos", np.float64), ("speed", np.float64),
+                                ("tilt_cos", np.float64), ("cost", np.float64)], align=True)
+"""Binary layout of ``mpcq_blackbox_rule`` (include/mpcq.h)."""
+
+
+def blackbox_rules(count: int, status_mask=0, fallback=False, nonfinite=True, err_pos=None, speed=None, tilt_cos=None, cost=None) -> np.ndarray:
+    """`count` rules for Engine.blackbox_start; every argument a scalar or [count].  status_mask: the status bits that raise BB_STATUS
+    (0: off); fallback, nonfinite: whether a fallback solve / a non-finite measurement, control or cost fires; err_pos [m], speed [m/s],
+    tilt_cos (cosine of the angle between body z and world z) and cost: thresholds, None or NaN (per entry) for a cause that is off."""
+    r = np.zeros(count, BLACKBOX_RULE_DTYPE)
+    r["status_mask"] = status_mask
+    r["causes"] = np.where(r["status_mask"] != 0, BB_STATUS, 0)
+    r["causes"] |= np.where(np.broadcast_to(np.asarray(fallback, dtype=bool), (count,)), BB_FALLBACK, 0).astype(np.int32)
+    r["causes"] |= np.where(np.broadcast_to(np.asarray(nonfinite, dtype=bool), (count,)), BB_NONFINITE, 0).astype(np.int32)
+    for name, bit, v in (("err_pos", BB_ERR_POS, err_pos), ("speed", BB_SPEED, speed), ("tilt_cos", BB_TILT, tilt_cos), ("cost", BB_COST, cost)):
+        if v is None:
+            continue
+        v = np.broadcast_to(np.asarray(v, dtype=np.float64), (count,))
+        on = ~np.isnan(v)
+        r[name] = np.where(on, v, 0.0)
+        r["causes"] |= np.where(on, bit, 0).astype(np.int32)
+    return r
+
+
+def blackbox_causes(rows, rules) -> np.ndarray:
+    """The device's judge on the host: the cause word [count, T] (int32) of every row of a record_get()-shaped dict `rows` (x_odom, x_ref,
+    w_odom, cost_solution, status, qp_iter -- a key is needed only if a cause that reads it is enabled) under rules [count] of
+    BLACKBOX_RULE_DTYPE, with the device's expressions in the device's order: numpy rounds every operation on its own, as the kernel
+    does.  The first period at which a quadrotor's word is non-zero is where its black box fires, with that word as the cause; tune
+    thresholds on a recording with it."""
+    rules = np.asarray(rules)
+    en = rules["causes"].astype(np.int32)[:, None]
+    shape = None
+    for k in ("x_odom", "cost_solution", "status", "qp_iter", "w_odom", "x_ref"):
+        if k in rows:
+            shape = np.asarray(rows[k]).shape[:2]
+            break
+    if shape is None:
+        raise ValueError("rows holds none of the fields the rule reads")
+    if shape[0] != len(rules):
+        raise ValueError(f"rows is for {shape[0]} quadrotors, rules for {len(rules)}")
+    c = np.zeros(shape, np.int32)
+
+    def need(bit, *keys):
+        if not (en & bit).any():
+            return False
+        missing = [k for k in keys if k not in rows]
+        if missing:
+            raise ValueError(f"cause {bit} is enabled and rows lacks {missing}")
+        return True
+
+    def th(name):
+        return rules[name].astype(np.float64)[:, None]
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        if need(BB_STATUS, "status"):
+            c |= np.where((np.asarray(rows["status"]).astype(np.int32) & rules["status_mask"].astype(np.int32)[:, None]) != 0, BB_STATUS, 0).astype(np.int32)
+        if need(BB_FALLBACK, "qp_iter"):
+            c |= np.where(np.asarray(rows["qp_iter"]).astype(np.int64) // 1000 % 10 != 0, BB_FALLBACK, 0).astype(np.int32)
+        if need(BB_NONFINITE, "x_odom", "w_odom", "cost_solution"):
+            fin = np.isfinite(rows["x_odom"]).all(axis=2) & np.isfinite(rows["w_odom"]).all(axis=2) & np.isfinite(rows["cost_solution"])
+            c |= np.where(~fin, BB_NONFINITE, 0).astype(np.int32)
+        if need(BB_ERR_POS, "x_odom", "x_ref"):
+            d = np.asarray(rows["x_odom"], dtype=np.float64)[:, :, 0:3] - np.asarray(rows["x_ref"], dtype=np.float64)[:, :, 0:3]
+            s = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]
+            c |= np.where(s > th("err_pos") * th("err_pos"), BB_ERR_POS, 0).astype(np.int32)
+        if need(BB_SPEED, "x_odom"):
+            v = np.asarray(rows["x_odom"], dtype=np.float64)[:, :, 7:10]
+            s = (v[:, :, 0] * v[:, :, 0] + v[:, :, 1] * v[:, :, 1]) + v[:, :, 2] * v[:, :, 2]
+            c |= np.where(s > th("speed") * th("speed"), BB_SPEED, 0).astype(np.int32)
+        if need(BB_TILT, "x_odom"):
+            qx, qy = np.asarray(rows["x_odom"], dtype=np.float64)[:, :, 4], np.asarray(rows["x_odom"], dtype=np.float64)[:, :, 5]
+            c |= np.where(1 - 2 * (qx * qx + qy * qy) < th("tilt_cos"), BB_TILT, 0).astype(np.int32)
+        if need(BB_COST, "cost_solution"):
+            c |= np.where(np.asarray(rows["cost_solution"], dtype=np.float64) > th("cost"), BB_COST, 0).astype(np.int32)
+    return c & en
