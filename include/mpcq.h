@@ -154,7 +154,7 @@ const char* mpcq_last_error(void);
  * trainer (csrc/mpcq_train.hpp with csrc/mpcq_learn_core.hpp, which mpcq_learn.hip shares).  The number stays 0.6.7 with the trainer:
  * tests/test_score.py pins it; the eight digits tell a library with the trainer from one without.  The same holds for the fleet
  * (mpcq_fleet_*, csrc/mpcq_fleet.hpp), which joined the eight digits after the trainer, and for the exploration (mpcq_explore_*,
- * csrc/mpcq_explore.hpp), which joined them after the fleet. */
+ * csrc/mpcq_explore.hpp), which joined them after the fleet, and the sensor (mpcq_sensor_*, csrc/mpcq_sensor.hpp) after that. */
 const char* mpcq_version(void);
 
 /* ---- lifetime.  quad_optimizer.__init__ (src/quad_opt.py:36-160): builds constants, K_x^-1,
@@ -693,6 +693,62 @@ int mpcq_fleet_set(mpcq_engine* e, const mpcq_plant* plants /*[B]*/, uint64_t pl
 int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants /*[B] or NULL*/, uint64_t plant_size, int64_t* period /*or NULL*/);
 /* back to the engine's shared plant; launches as before this change.  MPCQ_ERR_STATE: no fleet set. */
 int mpcq_fleet_stop(mpcq_engine* e);
+
+/* ---- the sensor: noise, bias, latency and dropout between the plant and the controller.  Without it the closed loop of mpcq_sim_steps
+ * measures the identity: the step solves from the plant's own state, exactly and at once.  A sensor is a table of B mpcq_sensor on the
+ * device; while one runs, one launch of a kernel of its own (csrc/mpcq_sensor.hpp) stands in front of every control period of
+ * mpcq_sim_steps / mpcq_sim_control_periods and turns the true plant state into the measurement the step solves from.  The step kernel
+ * takes its measurement by pointer and is untouched.  State x = [p(3), q(4, w first), v(3), r(3)]; sensor period n starts at period0;
+ * quadrotor b has the global index i = index0 + b.
+ *   Draws.  Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85), counter (n lo32, n hi32, i lo32, c), key
+ * (seed lo32, seed hi32), c = 0..3.  A word w becomes u = (w + 0.5) 2^-32 (exact in double, never 0 or 1).  Calls c = 0, 1, 2 give the
+ * normals z[4c .. 4c+3]: from the words (w0, w1) rho = sqrt(-2 ln u0), z = rho cos(6.283185307179586 u1), then rho sin(same); the words
+ * (w2, w3) likewise.  Word 0 of call 3 is u_drop.  The draws depend on (seed, n, i) only: not on the batch, a shard, a group or the
+ * order of launches.
+ *   Sample m_n.  p, v, r: x + bias + sigma z with z[0:3], z[6:9], z[9:12].  Attitude: theta = bias_att + sigma_att z[3:6], a = |theta|,
+ * q_m = normalise(q (x) [cos(a/2), sin(a/2) theta / a]) (the identity rotation for a = 0).  A channel (p, att, v, r) whose sigma and bias
+ * are all zero is copied, not computed: an all-zero sensor is the identity bit for bit.
+ *   Ring.  m_n goes to slot (n - period0) mod depth.
+ *   Delivery.  The candidate is m_max(n - delay, period0).  A period is dropped if n > period0 and (u_drop < p_drop or out_from <= n <
+ * out_to): the delivered measurement stays as it was and age += 1.  Otherwise delivered = candidate and age = min(delay, n - period0).
+ * Both comparisons are exact, so the drop pattern is reproducible bit for bit.
+ *   Who reads what.  The step, the recorder's rows, the black box's rows and the exploration read the measurement, as a real log would;
+ * the step kernel's own tracking accumulators (mpcq_get_tracking_stats) too.  The mission plans from the true plant state.  The
+ * scoreboard and the black box's judge read the measurement under MPCQ_SENSOR_JUDGE_MEASURED and the true plant state (mpcq_sim_get_state)
+ * under MPCQ_SENSOR_JUDGE_TRUTH -- in every control period, those of mpcq_step / mpcq_step_device_async included.
+ *   Period order with a sensor: sensor -> recorder / black box snapshots -> step -> rows -> score -> exploration -> plant -> mission.  Every
+ * plant update of mpcq_sim_steps is a launch of its own then, as with a fleet.  mpcq_step / mpcq_step_device_async take the caller's
+ * measurement and do not advance the sensor: a host loop is mpcq_sensor_sample -> mpcq_step -> mpcq_sim_plant_period, and flies bit for
+ * bit what mpcq_sim_steps flies.  mpcq_sim_run (one persistent launch) measures through no sensor: MPCQ_ERR_STATE while one runs.
+ * mpcq_reset and mpcq_sim_reset keep the table, the ring and the sensor period; mpcq_destroy frees them.  With no sensor started every
+ * launch sequence is what it was.  Device memory: 104 (depth + 1) + 224 bytes per quadrotor. */
+typedef struct mpcq_sensor {            /* one quadrotor's sensor; all zero = the identity */
+  double sigma_p[3], sigma_att[3], sigma_v[3], sigma_r[3];  /* white noise per period, std dev; att: rotation vector [rad], body frame */
+  double bias_p[3],  bias_att[3],  bias_v[3],  bias_r[3];   /* constant offsets */
+  double p_drop;                        /* probability that a period delivers nothing, [0, 1] */
+  int32_t delay;                        /* periods between sampling and delivery, 0 .. depth-1 */
+  int32_t reserved;
+  int64_t out_from, out_to;             /* outage: nothing delivered in sensor periods [out_from, out_to) */
+} mpcq_sensor;
+#define MPCQ_SENSOR_JUDGE_MEASURED 0    /* score and black box judge what the controller saw (what a real log holds) */
+#define MPCQ_SENSOR_JUDGE_TRUTH    1    /* score launch and the black box's judge read the true plant state */
+/* Start (or, while one runs, replace) the sensor: sensors [B] (sensor_size = the caller's sizeof(mpcq_sensor)), the seed of the draws,
+ * the global index of quadrotor 0, the first sensor period, the depth of the ring (1..32) and who judges.  The ring starts empty, the
+ * delivered measurement and age are zero until the first period.  MPCQ_ERR_INVALID, with the engine left as it was -- a running sensor
+ * goes on delivering what it would have -- and mpcq_last_error() naming the quadrotor and the field: sensors NULL, a sensor_size that is
+ * not this library's, a sigma that is negative or not finite, a bias that is not finite, p_drop outside [0, 1], delay outside
+ * 0..depth-1, depth outside 1..32, an unknown judge, a negative period0 or index0.  MPCQ_ERR_DEVICE: the buffers cannot be allocated. */
+int mpcq_sensor_start(mpcq_engine* e, const mpcq_sensor* sensors /*[B]*/, uint64_t sensor_size, uint64_t seed,
+                      int64_t index0 /*global index of quadrotor 0*/, int64_t period0, int32_t depth /*1..32*/, int32_t judge);
+/* The delivered measurement, its age in periods and the number of the NEXT sensor period, behind everything the engine has enqueued.
+ * MPCQ_ERR_STATE: no sensor running. */
+int mpcq_sensor_get(mpcq_engine* e, double* x_meas /*[B,13] or NULL*/, int32_t* age /*[B] or NULL*/, int64_t* period /*or NULL*/);
+/* One sensor launch on the current plant state; advances the sensor period and returns the delivered measurement: for host loops of
+ * mpcq_step + mpcq_sim_plant_period.  MPCQ_ERR_STATE: no sensor running; MPCQ_ERR_INVALID: x_meas NULL. */
+int mpcq_sensor_sample(mpcq_engine* e, double* x_meas /*[B,13]*/);
+/* Sensor off, buffers freed: the measurement is the identity again and period launches are what they are without it.  MPCQ_ERR_STATE:
+ * no sensor running. */
+int mpcq_sensor_stop(mpcq_engine* e);
 
 /* ---- exploration: mission limits from each quadrotor's envelope.  The reference's exploration loop (src/explore_trajectories.py:59-125)
  * flies one flight, trains a GP on that run and asks Explorer (src/Explorer.py:23-84) how far the training inputs reach in body-frame

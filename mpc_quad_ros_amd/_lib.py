@@ -147,6 +147,10 @@ SYMBOLS = [
     ("mpcq_fleet_set", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int64]),
     ("mpcq_fleet_get", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _lp]),
     ("mpcq_fleet_stop", ctypes.c_int, [_vp]),
+    ("mpcq_sensor_start", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    ("mpcq_sensor_get", ctypes.c_int, [_vp, _dp, _ip, _lp]),
+    ("mpcq_sensor_sample", ctypes.c_int, [_vp, _dp]),
+    ("mpcq_sensor_stop", ctypes.c_int, [_vp]),
     ("mpcq_explore_start", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _dp, _lp]),
     ("mpcq_explore_get", ctypes.c_int, [_vp, _dp, _lp, _dp]),
     ("mpcq_explore_stop", ctypes.c_int, [_vp]),

@@ -32,6 +32,7 @@
 #include "mpcq_predict.hpp"
 #include "mpcq_train.hpp"
 #include "mpcq_fleet.hpp"
+#include "mpcq_sensor.hpp"
 
 namespace mpcq {   // mpcq_spec.hip, one translation unit per specialised shape
 template <typename T> using StepFn = void (*)(const DevModel<T>, const DevState<T>, const int);
@@ -239,6 +240,7 @@ struct Tick {
   int mper = -1;        // the mission's period number (-1: no mission)
   long long sper = -1;   // the scoreboard's period number (-1: no score running)
   long long fper = -1;   // the fleet period of the plant update (-1: no fleet, or no plant update drawn)
+  long long nper = -1;   // the sensor period of the measurement (-1: no sensor, or the period takes the caller's measurement)
 };
 
 // ---- flight recorder (mpcq_record_*, mpcq_record.hpp): host bookkeeping and device buffers of a recording; the launches depend on the
@@ -400,6 +402,32 @@ static void fleet_launch(const Fleet& fl, const EngineView& v, int B, hipStream_
   hipLaunchKernelGGL(mpcq::fleet::fleet_plant_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a);
 }
 
+// ---- the sensor (mpcq_sensor_*, mpcq_sensor.hpp): noise, bias, latency and dropout between plant and controller.  The table in its
+// field-major device form, the ring of samples, the delivered measurement (what the step of mpcq_sim_steps solves from) and its age.
+struct Sensor {
+  bool on = false;
+  int depth = 1, judge = MPCQ_SENSOR_JUDGE_MEASURED;
+  long long period = 0, period0 = 0, index0 = 0;   // the next sensor period; the first; the global index of quadrotor 0
+  uint64_t seed = 0;
+  DevBuf<double> d_tab;      // [sensor::NF][B]
+  DevBuf<long long> d_win;   // [sensor::NI][B]: out_from | out_to
+  DevBuf<int> d_int;         // delay [B] | age [B]
+  DevBuf<double> d_ring;     // the ring [depth][13][B] | the delivered measurement [B][13]: out(B)
+  // The layout of d_ring and d_int as sensor_kernel knows them: the delivered measurement behind the ring, age behind delay
+  double* out(size_t B) const { return d_ring.p + (size_t)depth * 13 * B; }
+  int* age(size_t B) const { return d_int.p + B; }
+};
+// In front of everything else a control period issues: sensor period nper for the quadrotors [b0, b0 + n) of B, from the plant state
+// v.plant into sn.out(B).  The measurement is float64 in both precisions: nothing here depends on the engine's.
+static void sensor_launch(const Sensor& sn, const EngineView& v, int B, hipStream_t s, int b0, int n, long long nper) {
+  mpcq::sensor::Args a;
+  a.tab = sn.d_tab.p; a.win = sn.d_win.p; a.ints = sn.d_int.p; a.B = B; a.b0 = b0; a.n = n; a.depth = sn.depth;
+  a.period = nper; a.since = nper - sn.period0; a.index0 = sn.index0;
+  a.key0 = (unsigned)(sn.seed & 0xffffffffull); a.key1 = (unsigned)(sn.seed >> 32);
+  a.x = v.plant; a.ring = sn.d_ring.p;
+  hipLaunchKernelGGL(mpcq::sensor::sensor_kernel, dim3((n + 63) / 64), dim3(64), 0, s, a);
+}
+
 // ---- staging of the replan entry points (mpcq_replan, mpcq_replan_nonlinear, mpcq_replan_circle) and of mpcq_replace_trajectories
 struct ReplanStaging {
   DevBuf<double> d_in;    // replan: the caller's part (waypoints [B,n_wp,3], or radius [B] | v_max [B]) | starts [B,3] | extra; replace: the rows
@@ -461,10 +489,12 @@ struct mpcq_engine : EngineQueues {
   Score sc;                      // mpcq_score_start .. mpcq_score_stop
   Fleet fl;                      // mpcq_fleet_set .. mpcq_fleet_stop
   Explore ex;                    // mpcq_explore_start .. mpcq_explore_stop (or the end of the mission: end_exploration)
+  Sensor sn;                     // mpcq_sensor_start .. mpcq_sensor_stop
   // The ticket of the period about to be issued, the one place the features' counters advance.  control: a control period (mpcq_step,
   // mpcq_step_device_async, every period of mpcq_sim_steps) -- the recorder, the black box, the mission and the score count it. plant: a plant update
-  // (every period of mpcq_sim_steps, mpcq_sim_plant_period) -- the fleet period advances with it, never with a step alone.
-  Tick next_tick(bool control, bool plant) {
+  // (every period of mpcq_sim_steps, mpcq_sim_plant_period) -- the fleet period advances with it, never with a step alone.  sense: a
+  // measurement through the sensor (every period of mpcq_sim_steps, mpcq_sensor_sample) -- never a step that takes the caller's.
+  Tick next_tick(bool control, bool plant, bool sense = false) {
     Tick t;
     if (control) {
       t.row = rec.next_row();
@@ -473,6 +503,7 @@ struct mpcq_engine : EngineQueues {
       if (sc.on) t.sper = sc.periods++;
     }
     if (plant && fl.on) t.fper = fl.period++;
+    if (sense && sn.on) t.nper = sn.period++;
     return t;
   }
   // An exploration ends with the mission it explores for, or when that mission's queue is replaced: its launch writes limits into the
@@ -699,7 +730,7 @@ int box_init(mpcq_engine* e, const int* d_mask, long long first) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   return 0;
 }
-// What the six *_stop entry points do with their feature f of e (not_on: the error of a feature that is not on)
+// What the seven *_stop entry points do with their feature f of e (not_on: the error of a feature that is not on)
 template <typename F> int feature_stop(mpcq_engine* e, F& f, const char* not_on) {
   if (!f.on) return fail(MPCQ_ERR_STATE, not_on);
   HIP_TRY(hipStreamSynchronize(e->stream));   // (launches of an mpcq_step_device_async may still use the feature's buffers)
@@ -1100,8 +1131,9 @@ struct EngineT : mpcq_engine {
     hipLaunchKernelGGL(mpcq::record::record_snapshot_kernel, dim3((n * mpcq::record::SNAP + 63) / 64), dim3(64), 0, s, (const int*)bb.d_sel.p, j0, n,
                        (const double*)st.xpp, (const int*)st.has_prev, bb.d_snap.p);
   }
-  // behind the recorder's row, in front of the score: period `per` into ring slot `slot` of whoever is not frozen, then the judge
-  void bb_write(hipStream_t s, int j0, int j1, int slot, long long per, const double* xmeas) {
+  // behind the recorder's row, in front of the score: period `per` into ring slot `slot` of whoever is not frozen, then the judge (judged:
+  // what it judges -- the measurement, or under MPCQ_SENSOR_JUDGE_TRUTH the plant state)
+  void bb_write(hipStream_t s, int j0, int j1, int slot, long long per, const double* xmeas, const double* judged) {
     namespace bx = mpcq::blackbox;
     const int n = j1 - j0;
     if (n <= 0) return;
@@ -1113,7 +1145,7 @@ struct EngineT : mpcq_engine {
     bx::JudgeArgs g;
     g.sel = bb.d_sel.p; g.j0 = j0; g.n = n; g.rules = bb.d_rules.p; g.st = bb.state();
     g.period = per; g.post = bb.post;
-    g.xmeas = xmeas; g.w = st.w; g.cost = st.cost; g.traj = st.traj;
+    g.xmeas = judged; g.w = st.w; g.cost = st.cost; g.traj = st.traj;
     g.tlen = st.tlen; g.idx = st.idx; g.status = st.status; g.qp_iter = st.qp_iter;
     g.Tmax = m.Tmax; g.N = N; g.skip = m.skip;
     hipLaunchKernelGGL(bx::judge_kernel, dim3((n + 63) / 64), dim3(64), 0, s, g);
@@ -1140,25 +1172,28 @@ struct EngineT : mpcq_engine {
   // The optional events of a period (see period)
   struct PeriodEvents { hipEvent_t front = nullptr, step = nullptr, end = nullptr; };
   // One period of groups[gi], the only place that issues one.  On the group's stream, in this order:
-  //   the recorder's snapshot (t.row >= 0: the period is recorded) -> the black box's snapshot (t.bslot >= 0: a black box runs) -> ev.front
+  //   the sensor's launch (t.nper >= 0: the period measures through the sensor; s.x_meas is its output then) -> the recorder's snapshot (t.row >= 0: the period is recorded) -> the black box's snapshot (t.bslot >= 0: a black box runs) -> ev.front
   //   -> ordering launch -> ev.step -> step kernel -> ev.end -> the recorder's row -> the black box's row and judge launches
   //   -> the scoreboard's launch (t.sper >= 0) -> the exploration launch (an exploration runs and t.mper >= 0)
   //   -> the plant update (plant: s.run_nsub substeps of s.run_dt on s.run_x; with t.fper >= 0 the fleet's launch, plant_launch)
   //   -> the mission launch (t.mper >= 0; the flights start at the plant state behind its update, or without a plant at the period's
   //   measurement).
+  // Under MPCQ_SENSOR_JUDGE_TRUTH the scoreboard and the black box's judge read the plant state (judged) where the rows read s.x_meas.
   // The caller asks hipGetLastError once it has issued all it has to issue.
   int period(int gi, const mpcq::DevState<T>& s, int mode, const Tick& t, const PeriodEvents& ev, bool plant) {
     const Group& g = groups[gi];
     if (g.n <= 0) return 0;
     const EngineView v = view();
+    const double* judged = sn.on && sn.judge == MPCQ_SENSOR_JUDGE_TRUTH ? v.plant : s.x_meas;
+    if (t.nper >= 0) sensor_launch(sn, v, B, g.stream, g.b0, g.n, t.nper);
     if (t.row >= 0) rec_snapshot(g.stream, rec.glo[gi], rec.ghi[gi]);
     if (t.bslot >= 0) bb_snapshot(g.stream, bb.glo[gi], bb.ghi[gi]);
     if (ev.front) HIP_TRY(hipEventRecord(ev.front, g.stream));
     launch_period(s, mode, ev.step, g.stream, g.b0, g.n);
     if (ev.end) HIP_TRY(hipEventRecord(ev.end, g.stream));
     if (t.row >= 0) rec_write(g.stream, rec.glo[gi], rec.ghi[gi], t.row, s.x_meas);
-    if (t.bslot >= 0) bb_write(g.stream, bb.glo[gi], bb.ghi[gi], t.bslot, t.bper, s.x_meas);
-    if (t.sper >= 0) score_launch(sc, v, B, g.stream, g.b0, g.n, t.sper, s.x_meas);
+    if (t.bslot >= 0) bb_write(g.stream, bb.glo[gi], bb.ghi[gi], t.bslot, t.bper, s.x_meas, judged);
+    if (t.sper >= 0) score_launch(sc, v, B, g.stream, g.b0, g.n, t.sper, judged);
     if (ex.on && t.mper >= 0) explore_launch(ex, ms, v, B, g.stream, g.b0, g.n, s.x_meas);
     if (plant) plant_launch(g.stream, g.b0, g.n, s.run_x, s.run_nsub, s.run_dt, t.fper);
     if (t.mper >= 0) mission_launch(ms, v, B, g.stream, g.b0, g.n, plant ? s.run_x : s.x_meas, t.mper);
@@ -1252,7 +1287,7 @@ struct EngineT : mpcq_engine {
   int sim_steps(int K, int n_sub, double sim_dt) override {
     if (const int rc = needs_trajectories(this, "mpcq_sim_steps")) return rc;
     mpcq::DevState<T> s2 = st;
-    s2.x_meas = d_xs;
+    s2.x_meas = sn.on ? sn.out(B) : d_xs;   // (a sensor's launch in front of every period turns d_xs into its output)
     // HIP events around every 4th step-kernel launch: an event pair between two dependent launches costs dispatch overlap (measured
     // at B = 1 024, 20 launches: pairs on every launch 3.18 M steps/s, on every 2nd 3.22, every 4th 3.25, none 3.26), so only a sample of
     // the launches carries one (calls of fewer than 8 periods: every launch; MPCQ_KEV_STRIDE under MPCQ_TUNING=1 overrides)
@@ -1266,7 +1301,9 @@ struct EngineT : mpcq_engine {
     // (split_plant, see create): every update is a launch of the plant kernel.  Same arithmetic, same results either way.
     // An active mission plans from the plant state behind the period's update, so it needs that update in front of its launch: every
     // update is a launch then, too.  A fleet's plants are integrated by a kernel of their own (mpcq_fleet.hpp): every update is its launch.
-    const bool split = split_plant || ms.on || fl.on;
+    // A sensor measures the plant state in front of the step (MODE_PLANT_FIRST would measure from the buffer it is about to integrate): every
+    // update is a launch then, too.
+    const bool split = split_plant || ms.on || fl.on || sn.on;
     s2.run_x = d_xs; s2.run_steps = 1; s2.run_nsub = n_sub; s2.run_dt = sim_dt;
     // Groups (see init): the K periods {order, step, plant} of a group go to its stream, issued period by period round the groups so that
     // the host feeds every queue.  The group streams start behind everything issued on the engine's stream and the engine's stream
@@ -1277,7 +1314,7 @@ struct EngineT : mpcq_engine {
     for (int g = 1; g < G; ++g) HIP_TRY(hipStreamWaitEvent(groups[g].stream, gstart, 0));
     int rc;
     for (int k = 0; k < K; ++k) {
-      const Tick tick = next_tick(true, true);   // (one ticket per control period, the same for every group: the recorder's launches of a group cover the selection inside it)
+      const Tick tick = next_tick(true, true, true);   // (one ticket per control period, the same for every group: the recorder's launches of a group cover the selection inside it)
       const int mode = mpcq::MODE_TRAJ | mpcq::MODE_POST | base_mode() | ((!split && k > 0) ? mpcq::MODE_PLANT_FIRST : 0);
       for (int g = 0; g < G; ++g) {
         PeriodEvents ev;
@@ -1312,6 +1349,7 @@ struct EngineT : mpcq_engine {
     if (ms.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a mission (one persistent launch): mpcq_mission_stop first, or use mpcq_sim_steps");
     if (sc.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot score flights (one persistent launch): mpcq_score_stop first, or use mpcq_sim_steps");
     if (fl.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot fly a fleet (one persistent launch): mpcq_fleet_stop first, or use mpcq_sim_steps");
+    if (sn.on) return fail(MPCQ_ERR_STATE, "mpcq_sim_run cannot measure through a sensor (one persistent launch): mpcq_sensor_stop first, or use mpcq_sim_steps");
     if (K <= 0) return 0;
     mpcq::DevState<T> s2 = st;
     s2.x_meas = d_xs;
@@ -2315,6 +2353,91 @@ int mpcq_fleet_get(mpcq_engine* e, mpcq_plant* plants, uint64_t plant_size, int6
   return 0;
 }
 int mpcq_fleet_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->fl, "mpcq_fleet_stop: no fleet set"); }
+
+// ---- the sensor (mpcq_sensor.hpp; state and launch: Sensor, sensor_launch, in front of every period of mpcq_sim_steps: EngineT::period)
+int mpcq_sensor_start(mpcq_engine* e, const mpcq_sensor* sensors, uint64_t sensor_size, uint64_t seed, int64_t index0, int64_t period0, int32_t depth,
+                      int32_t judge) {
+  ENTER(e);
+  namespace sr = mpcq::sensor;
+  if (!sensors) return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: sensors is NULL");
+  if (sensor_size != sizeof(mpcq_sensor))
+    return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: sensor_size " + std::to_string(sensor_size) + " is not this library's sizeof(mpcq_sensor) = " + std::to_string(sizeof(mpcq_sensor)));
+  if (depth < 1 || depth > sr::MAX_DEPTH) return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: depth " + std::to_string(depth) + " outside 1..32");
+  if (judge != MPCQ_SENSOR_JUDGE_MEASURED && judge != MPCQ_SENSOR_JUDGE_TRUTH)
+    return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: judge must be MPCQ_SENSOR_JUDGE_MEASURED (0) or MPCQ_SENSOR_JUDGE_TRUTH (1)");
+  if (period0 < 0) return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: period0 must be >= 0");
+  if (index0 < 0) return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: index0 must be >= 0");
+  const size_t B = e->B;
+  // every rule is checked before anything of the engine changes
+  for (size_t b = 0; b < B; ++b) {
+    const mpcq_sensor& s = sensors[b];
+    auto bad = [&](const char* field, int i, const char* rule) {
+      return fail(MPCQ_ERR_INVALID, "mpcq_sensor_start: quadrotor " + std::to_string(b) + ": " + field + (i >= 0 ? "[" + std::to_string(i) + "]" : std::string()) + " " + rule);
+    };
+    struct Field { const char* name; const double* v; int n; int rule; };   // rule 1: >= 0; 2: in [0, 1]
+    const Field fields[] = {{"sigma_p", s.sigma_p, 3, 1}, {"sigma_att", s.sigma_att, 3, 1}, {"sigma_v", s.sigma_v, 3, 1}, {"sigma_r", s.sigma_r, 3, 1},
+                            {"bias_p", s.bias_p, 3, 0}, {"bias_att", s.bias_att, 3, 0}, {"bias_v", s.bias_v, 3, 0}, {"bias_r", s.bias_r, 3, 0},
+                            {"p_drop", &s.p_drop, 1, 2}};
+    for (const Field& f : fields)
+      for (int i = 0; i < f.n; ++i) {
+        const int at = f.n > 1 ? i : -1;
+        if (!std::isfinite(f.v[i])) return bad(f.name, at, "is not finite");
+        if (f.rule == 1 && !(f.v[i] >= 0)) return bad(f.name, at, "must be >= 0");
+        if (f.rule == 2 && !(f.v[i] >= 0 && f.v[i] <= 1)) return bad(f.name, at, "must be in [0, 1]");
+      }
+    if (s.delay < 0 || s.delay > depth - 1) return bad("delay", -1, ("must be in 0..depth-1 = 0.." + std::to_string(depth - 1)).c_str());
+  }
+  std::vector<double> tab((size_t)sr::NF * B), row(sr::NF);
+  std::vector<long long> win((size_t)sr::NI * B);
+  std::vector<int> ints(2 * B, 0);   // delay | age
+  for (size_t b = 0; b < B; ++b) {
+    sr::pack(sensors[b], row.data());
+    for (int f = 0; f < sr::NF; ++f) tab[(size_t)f * B + b] = row[f];
+    win[(size_t)sr::I_FROM * B + b] = sensors[b].out_from; win[(size_t)sr::I_TO * B + b] = sensors[b].out_to;
+    ints[b] = sensors[b].delay;
+  }
+  // The new sensor is built beside the running one and takes its place only once it is complete on the device: a failed allocation or
+  // copy leaves the engine measuring through the sensor it had.
+  Sensor fresh;
+  auto need = [](auto& buf, size_t elems) { return grow_or_fail(buf, elems, "mpcq_sensor_start: cannot allocate " + std::to_string(elems * sizeof(*buf.p)) + " bytes"); };
+  int rc;
+  if ((rc = need(fresh.d_tab, tab.size())) || (rc = need(fresh.d_win, win.size())) || (rc = need(fresh.d_int, ints.size())) ||
+      (rc = need(fresh.d_ring, ((size_t)depth + 1) * 13 * B)))
+    return rc;
+  hipStream_t s = e->stream;
+  HIP_TRY(hipMemcpyAsync(fresh.d_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(fresh.d_win.p, win.data(), win.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(fresh.d_int.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(fresh.d_ring.p, 0, ((size_t)depth + 1) * 13 * B * sizeof(double), s));
+  HIP_TRY(hipStreamSynchronize(s));   // (behind it nothing the engine has enqueued reads the buffers that are replaced)
+  fresh.on = true;
+  fresh.depth = depth; fresh.judge = judge; fresh.seed = seed;
+  fresh.period = fresh.period0 = period0; fresh.index0 = index0;
+  e->sn = std::move(fresh);
+  return 0;
+}
+int mpcq_sensor_get(mpcq_engine* e, double* x_meas, int32_t* age, int64_t* period) {
+  ENTER(e);
+  const Sensor& sn = e->sn;
+  if (!sn.on) return fail(MPCQ_ERR_STATE, "mpcq_sensor_get: no sensor running");
+  const size_t B = e->B;
+  if (x_meas) HIP_TRY(hipMemcpyAsync(x_meas, sn.out(B), 13 * B * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (age) HIP_TRY(hipMemcpyAsync(age, sn.age(B), B * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (period) *period = sn.period;
+  return 0;
+}
+int mpcq_sensor_sample(mpcq_engine* e, double* x_meas) {
+  ENTER(e);
+  if (!e->sn.on) return fail(MPCQ_ERR_STATE, "mpcq_sensor_sample: no sensor running");
+  if (!x_meas) return fail(MPCQ_ERR_INVALID, "mpcq_sensor_sample: x_meas is NULL");
+  sensor_launch(e->sn, e->view(), e->B, e->stream, 0, e->B, e->next_tick(false, false, true).nper);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(x_meas, e->sn.out(e->B), (size_t)13 * e->B * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+int mpcq_sensor_stop(mpcq_engine* e) { ENTER(e); return feature_stop(e, e->sn, "mpcq_sensor_stop: no sensor running"); }
 
 // ---- RGP read-out (mpcq_predict.hpp; predict_run).  The engine's stream is behind every group stream of mpcq_sim_steps when that call
 // returns, and both calls run on it: they see the state after the last period.

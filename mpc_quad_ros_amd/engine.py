@@ -505,6 +505,38 @@ class Engine:
         from .params import fleet_drag_accel
         return fleet_drag_accel(self.fleet_get()[0], v)
 
+    # ---- the sensor: noise, bias, latency and dropout between the plant and the controller
+    def sensor_start(self, sensors, seed=0, index0=0, period0=0, depth=1, judge=0):
+        """Measure through sensors [B] of params.SENSOR_DTYPE (params.sensor_defaults / sensor_sample build them) in every period of
+        sim_steps / sim_control_periods from now on: the step, the recorder, the black box and the exploration see the delivered
+        measurement, not the plant state.  seed and index0 (the global index of quadrotor 0) select the draws, period0 is the first
+        sensor period, depth (1..32) the ring that latency reads from (every delay <= depth - 1); judge: params.SENSOR_JUDGE_MEASURED
+        (score and black box judge what the controller saw) or SENSOR_JUDGE_TRUTH (they read the true plant state).  Calling it again
+        replaces the sensor.  step() takes the caller's measurement: a host loop is sensor_sample -> step -> sim_plant_period."""
+        from .params import SENSOR_DTYPE
+        sensors = np.ascontiguousarray(sensors)
+        if sensors.dtype != SENSOR_DTYPE or sensors.shape != (self.B,):
+            raise ValueError(f"sensors must be a [B={self.B}] array of params.SENSOR_DTYPE")
+        self._check(self.lib.mpcq_sensor_start(self.h, sensors.ctypes.data_as(ctypes.c_void_p), SENSOR_DTYPE.itemsize, int(seed) & (2 ** 64 - 1),
+                                               int(index0), int(period0), int(depth), int(judge)))
+
+    def sensor_get(self):
+        """(the delivered measurement [B, 13], its age in periods [B], the number of the next sensor period)."""
+        x, age, period = np.zeros((self.B, NX)), np.zeros(self.B, np.int32), ctypes.c_int64()
+        self._check(self.lib.mpcq_sensor_get(self.h, _lib.d(x), _lib.i(age), ctypes.byref(period)))
+        return x, age, period.value
+
+    def sensor_sample(self):
+        """One sensor period on the current plant state: the delivered measurement [B, 13] (what the step of that period of sim_steps
+        would solve from)."""
+        x = np.zeros((self.B, NX))
+        self._check(self.lib.mpcq_sensor_sample(self.h, _lib.d(x)))
+        return x
+
+    def sensor_stop(self):
+        """Back to the identity: the step of sim_steps solves from the plant state."""
+        self._check(self.lib.mpcq_sensor_stop(self.h))
+
     # ---- exploration: the limits of the next mission leg from the envelope of body velocities the quadrotor has flown
     def explore_start(self, rules, leg_mask=None, env=None, samples=None):
         """Explore with the mission that is set (mpcq_explore_start): in the period a flight ends, v_max and a_max of the quadrotor's

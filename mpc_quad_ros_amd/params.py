@@ -270,6 +270,54 @@ def fleet_drag_accel(plants: np.ndarray, v) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------
+# The sensor (include/mpcq.h mpcq_sensor_*): white noise, bias, latency, dropout and an outage window per quadrotor, between the plant
+# and the controller of sim_steps.
+SENSOR_JUDGE_MEASURED, SENSOR_JUDGE_TRUTH = 0, 1
+SENSOR_DTYPE = np.dtype([
+    ("sigma_p", np.float64, (3,)), ("sigma_att", np.float64, (3,)), ("sigma_v", np.float64, (3,)), ("sigma_r", np.float64, (3,)),
+    ("bias_p", np.float64, (3,)), ("bias_att", np.float64, (3,)), ("bias_v", np.float64, (3,)), ("bias_r", np.float64, (3,)),
+    ("p_drop", np.float64), ("delay", np.int32), ("reserved", np.int32), ("out_from", np.int64), ("out_to", np.int64)], align=True)
+"""Binary layout of ``mpcq_sensor`` (include/mpcq.h)."""
+SENSOR_CHANNELS = ("p", "att", "v", "r")
+
+
+def sensor_defaults(count: int) -> np.ndarray:
+    """`count` sensors that measure the identity (all zero): flying them is bit for bit flying without a sensor."""
+    return np.zeros(count, SENSOR_DTYPE)
+
+
+def sensor_sample(seed: int, first_index: int, count: int, sigma=None, bias=None, p_drop_max: float = 0.0, delay_max: int = 0,
+                  outage_prob: float = 0.0, outage=(0, 0)) -> np.ndarray:
+    """Randomised sensors, quadrotors first_index .. first_index + count - 1 of a swarm.  Every quadrotor is drawn from a generator of
+    its own, seeded with (seed, global index), so shards of a swarm agree with the whole (as fleet_sample).
+      sigma        dict by channel ('p', 'att', 'v', 'r'): each of the three standard deviations uniform in [0, value]
+      bias         dict by channel: each of the three offsets normal with this standard deviation
+      p_drop_max   p_drop uniform in [0, p_drop_max]
+      delay_max    delay uniform in {0, .., delay_max} (sensor_start needs depth > delay_max)
+      outage_prob  with this probability the quadrotor has the outage window outage = (out_from, out_to)"""
+    s = sensor_defaults(count)
+    sigma, bias = dict(sigma or {}), dict(bias or {})
+    unknown = (set(sigma) | set(bias)) - set(SENSOR_CHANNELS)
+    if unknown or any(not v >= 0 for v in list(sigma.values()) + list(bias.values())):
+        raise ValueError("sigma and bias: values >= 0 by channel 'p', 'att', 'v', 'r'")
+    if not 0.0 <= p_drop_max <= 1.0 or not 0.0 <= outage_prob <= 1.0 or delay_max < 0:
+        raise ValueError("p_drop_max and outage_prob in [0, 1], delay_max >= 0")
+    for i in range(count):
+        rng = np.random.default_rng([int(seed), int(first_index) + i])
+        # (every draw is made whatever the options, so that one option does not move the others' values)
+        us, ns = rng.uniform(size=(4, 3)), rng.normal(size=(4, 3))
+        drop, delay, hit = rng.uniform(), rng.uniform(), rng.uniform()
+        for k, ch in enumerate(SENSOR_CHANNELS):
+            s["sigma_" + ch][i] = sigma.get(ch, 0.0) * us[k]
+            s["bias_" + ch][i] = bias.get(ch, 0.0) * ns[k] + 0.0   # (+ 0.0: no -0.0 where there is no bias)
+        s["p_drop"][i] = p_drop_max * drop
+        s["delay"][i] = min(int(delay * (delay_max + 1)), delay_max)
+        if hit < outage_prob:
+            s["out_from"][i], s["out_to"][i] = int(outage[0]), int(outage[1])
+    return s
+
+
+# ---------------------------------------------------------------------------------------------
 # Exploration (include/mpcq.h mpcq_explore_*): the limits of the next mission leg from the envelope of body velocities a quadrotor has
 # flown -- the reference's Explorer (src/Explorer.py:40-84) as src/explore_trajectories.py:59-125 applies it, per quadrotor on the device.
 EXPLORE_LAST_FLIGHT, EXPLORE_CUMULATIVE = 0, 1
