@@ -203,6 +203,7 @@ template <typename M> __device__ inline int qp_iter_pack(const M& m, const int c
 
 // Diagnostic build only (-DMPCQ_PROFILE, libmpcq_prof.so): per-phase shader-cycle totals per instance.
 enum : int { PF_LOAD = 0, PF_SHOOT_X, PF_SHOOT_S, PF_FACTOR, PF_FWD, PF_BWD, PF_ADJ, PF_ROLL, PF_ELEM, PF_POST, PF_TOTAL, PF_N = 16 };
+constexpr int PF_FORM = 15;   // block formation of the float interior point (blk_form), cycles.  (Slots 11..14 of the plain profile build are the counters of polish().)
 #ifdef MPCQ_PROFILE
 struct Prof { unsigned long long acc[PF_N]; unsigned long long t; int oth; };
 __device__ inline void pf_start(Prof& p) { p.t = __builtin_readcyclecounter(); }
@@ -322,6 +323,7 @@ struct Lds {
   int gk;                    // Riccati gains K, Lambda^-1 in the global record as well, and r0 / lb / ub inside the union (written behind the shooting)
   int mrow;                  // multiplier rows (always global): per stage 4 rows [M_a(13) | F_uu row(4) | gt_a | pad 2]
   int pst;                   // cost-to-go of every stage (always global): [P_i as accumulator tile (256) | p_i (16)]
+  int blk;                   // block records of the float interior point (always global, fp64 instances with N a multiple of 4): see blk_form
 };
 __host__ __device__ inline int al4(int v) { return (v + 3) & ~3; }
 // gab: 0 everything in LDS | 1 the stage records (AB'', c, qv) in the per-instance global record | 2 = 1 + the Riccati gains there too
@@ -380,6 +382,8 @@ __host__ __device__ inline Lds lds_layout(int N, int nb, int gab, int mixed = 0)
   if (mixed) L.dxd = (L.dbytes + L.dx * 4) / 8;
   if (L.gk) { L.K = gtake(N * KS); L.Linv = gtake(N * 16); }
   else { L.K = take(N * KS); L.Linv = take(N * 16); }
+  // four-stage block records of the fallback's float interior point: N / 4 blocks x 5 float tiles of 16 x 16 (= 128 doubles each)
+  L.blk = (!mixed && N > 0 && N % 4 == 0 && N * NU <= 128) ? gtake((N / 4) * 5 * 128) : 0;
   L.sF = take(4 * VS);
   L.sT = take(4 * VS);   // rows 10..12 of T1'' (+ one row the fp64 hand-over writes unconditionally and nobody reads)
   L.stv = take(2 * VS);
@@ -1494,6 +1498,245 @@ MPCQ_PHASE bool riccati_factor(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L
   return wave_min<int>(ok ? 1 : 0) != 0;   // all lanes agree on definiteness
 }
 
+// ------------------------------------------------------------------ float interior point on four-stage blocks
+// The float interior point of the fp64 instances (ipm_float_stage) only names a working set; its Newton systems (H + Sigma) d = -rho are
+// solved on the horizon condensed four stages at a time: block k has the state x_{4k} (13) and the inputs of stages 4k .. 4k+3 (16, one
+// matrix-core tile wide), so a factorisation and a sweep are N / 4 dependent block steps instead of N stage steps.  The horizon stays
+// sparse and the recursion a Riccati recursion (with the cross term S that condensing creates); only its stage width changes.
+//   blk_form (once per solve, the dynamics and the Hessian do not change between iterations): per block five float tiles
+//     Abar = A_3 A_2 A_1 A_0 | Bbar (13 x 16) | Qbar = sum Phi_j^T Q Phi_j | Sbar = sum Gam_j^T Q Phi_j (16 x 13) | Rbar = sum Gam_j^T Q Gam_j
+//     (Phi_j, Gam_j: the response of x_{4k+j} to x_{4k} and to the block's inputs; Rbar without the input weights, which arrive with Sigma)
+//   blk_factor: Lambda = Rbar + diag(R + Sigma) + Bbar^T P Bbar, M = Sbar + Bbar^T P Abar; block LDL^T of Lambda (4 x 4 blocks, L block
+//     unit lower, D block diagonal) in registers and on the matrix cores, applied to [M | g] and to the identity in the same pass:
+//     Z = L^-1 [M | g], Z2 = L^-1; then K = -Z2^T D^-1 Z (column 14: the feed-forward), Lambda^-1 = Z2^T D^-1 Z2,
+//     P = Qbar + Abar^T P Abar - Z^T D^-1 Z (column 14: p) -- all three products straight from the registers.
+//   blk_forward / blk_backward_vec: two matrix-vector chains per block.
+// Tiles are row-major 16 x 16 floats; "accumulator form" is t[s] = T[4h + s][c] (what mfma returns and takes as B operand, and as A
+// operand of T^T), "row form" t[s] = T[c][4h + s] (A operand of T, one 128-bit read).  -DMPCQ_BLOCK_IPM=0: the stage-wise iteration.
+#ifndef MPCQ_BLOCK_IPM
+#define MPCQ_BLOCK_IPM 1
+#endif
+constexpr int BT = 256, BREC = 5 * BT;                                    // a tile ; a block record
+constexpr int BK_A = 0, BK_B = BT, BK_Q = 2 * BT, BK_S = 3 * BT, BK_R = 4 * BT;
+template <typename C> constexpr bool blk_ipm() { return MPCQ_BLOCK_IPM != 0 && C::N > 0 && C::N % 4 == 0 && C::N * NU <= 128; }
+__device__ inline void tl_acc(P<float> p, int off, int h, int c, float (&t)[4]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) t[s] = p[off + (4 * h + s) * 16 + c];
+}
+__device__ inline void tl_acc_st(P<float> p, int off, int h, int c, const float (&t)[4]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) p[off + (4 * h + s) * 16 + c] = t[s];
+}
+__device__ inline void tl_row(P<float> p, int off, int h, int c, float (&t)[4]) {
+  const V4<float> v = ld4(p, off + c * 16 + 4 * h);
+  t[0] = v.a; t[1] = v.b; t[2] = v.c; t[3] = v.d;
+}
+__device__ inline void tl_mm(float (&acc)[4], const float (&a)[4], const float (&b)[4]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) mfma(acc, a[s], b[s]);
+}
+__device__ inline float dot4(const float (&a)[4], const float (&b)[4]) { return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]); }
+
+// Sf: float view of the LDS workspace (weights at Lf.wq) ; A: the double stage records ; Bk: float view of the global record
+template <typename C, typename PA>
+MPCQ_COLD void blk_form(P<float> Sf, PA A, P<float> Bk, const Lds& L, const Lds& Lf) {
+  constexpr int N = C::N;
+  const int lane = lane_id(), h = lane >> 4, c = lane & 15;
+  float qrow[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) qrow[s] = 4 * h + s < NX ? Sf[Lf.wq + (4 * h + s < NX ? 4 * h + s : 0)] : 0.0f;
+  for (int k = 0; k < N / 4; ++k) {
+    float Phi[4], Gam[4] = {0, 0, 0, 0}, Qb[4] = {0, 0, 0, 0}, Sb[4] = {0, 0, 0, 0}, Rb[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) Phi[s] = (4 * h + s == c && c < NX) ? 1.0f : 0.0f;
+    for (int j = 0; j < 4; ++j) {
+      float QP[4], QG[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { QP[s] = qrow[s] * Phi[s]; QG[s] = qrow[s] * Gam[s]; }
+      tl_mm(Qb, Phi, QP);
+      if (j > 0) { tl_mm(Sb, Gam, QP); tl_mm(Rb, Gam, QG); }
+      // stage 4k + j: [A | B] with the position columns of A as identity, as A operand (row form) ; B placed in columns 4j .. 4j + 3
+      const int base = L.AB + (4 * k + j) * ABS;
+      float Aop[4], nG[4], nP[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int row = 4 * h + s;
+        const float o = (float)A[base + (c < NX ? c : 0) * ABW + (row < 10 ? row : 0)];
+        Aop[s] = c < NX ? (row < 10 ? o : ((row < NX && row == c) ? 1.0f : 0.0f)) : 0.0f;
+        const float b = (float)A[base + (row < NX ? row : 0) * ABW + 10 + (c & 3)];
+        nG[s] = (row < NX && (c >> 2) == j) ? b : 0.0f;
+      }
+      tl_mm(nP, Aop, Phi);
+      tl_mm(nG, Aop, Gam);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { Phi[s] = nP[s]; Gam[s] = nG[s]; }
+    }
+    const int o = Lf.blk + k * BREC;
+    tl_acc_st(Bk, o + BK_A, h, c, Phi); tl_acc_st(Bk, o + BK_B, h, c, Gam);
+    tl_acc_st(Bk, o + BK_Q, h, c, Qb); tl_acc_st(Bk, o + BK_S, h, c, Sb); tl_acc_st(Bk, o + BK_R, h, c, Rb);
+  }
+  __syncthreads();
+}
+
+// One step of the block LDL^T of Lam by 4 x 4 diagonal blocks (block J = rows 4J .. 4J+3 = the registers of lane group J), applied to Y
+// and Z in the same pass.  The diagonal block D reaches every lane through v_readlane and is factorised redundantly (the 4 x 4 LDL^T of
+// riccati_factor); the lanes of group J then solve with it for their own column: G = C D^-1 (C = block column J, by symmetry their
+// registers of Lam) and the rows D^-1 Y_J, D^-1 Z_J (kept in VY, VZ: row block J of Y and Z is final here).  The rows below lose
+// G Y_J: one tile product per tile whose A operand is -G on lane group J and zero elsewhere.
+__device__ inline void blk_solve4(const float (&Lm)[4][4], const float (&id)[4], float (&y)[4]) {
+#pragma unroll
+  for (int cc = 1; cc < 4; ++cc) {
+#pragma unroll
+    for (int k = 0; k < cc; ++k) y[cc] -= Lm[cc][k] * y[k];
+  }
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) y[cc] *= id[cc];
+#pragma unroll
+  for (int cc = 2; cc >= 0; --cc) {
+#pragma unroll
+    for (int k = cc + 1; k < 4; ++k) y[cc] -= Lm[k][cc] * y[k];
+  }
+}
+template <int J> __device__ inline void blk_ldl_step(float (&Lam)[4], float (&Y)[4], float (&Z)[4], float (&VY)[4], float (&VZ)[4], const int h, const int c, bool& ok) {
+  float Lm[4][4], id[4], cm[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int q = 0; q <= a; ++q) Lm[a][q] = bc(Lam[a], 16 * J + 4 * J + q);
+#pragma unroll
+  for (int cc = 0; cc < 4; ++cc) {
+    float d = Lm[cc][cc];
+#pragma unroll
+    for (int k = 0; k < cc; ++k) d -= Lm[cc][k] * cm[cc][k];
+    if (!(d > 0.0f)) ok = false;
+    d = d > 0.0f ? d : 1.0f;
+    id[cc] = trcp1(d);
+#pragma unroll
+    for (int a = cc + 1; a < 4; ++a) {
+      float s2 = Lm[a][cc];
+#pragma unroll
+      for (int k = 0; k < cc; ++k) s2 -= Lm[a][k] * cm[cc][k];
+      cm[a][cc] = s2;
+      Lm[a][cc] = s2 * id[cc];
+    }
+  }
+  const bool mine = h == J;
+  float g[4], vy[4], vz[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { g[s] = Lam[s]; vy[s] = Y[s]; vz[s] = Z[s]; }
+  blk_solve4(Lm, id, vy); blk_solve4(Lm, id, vz);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { VY[s] = mine ? vy[s] : VY[s]; VZ[s] = mine ? vz[s] : VZ[s]; }
+  if constexpr (J < 3) {
+    blk_solve4(Lm, id, g);
+    const bool below = mine && c >= 4 * (J + 1);
+    float w[4], oL[4], oY[4], oZ[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { w[s] = below ? -g[s] : 0.0f; oL[s] = Lam[s]; oY[s] = Y[s]; oZ[s] = Z[s]; }
+    tl_mm(Lam, w, oL); tl_mm(Y, w, oY); tl_mm(Z, w, oZ);
+  }
+}
+
+// Backward block recursion for diag(R + Sigma) in Sf[Lf.rt] and the linear term Sf[Lf.rho]: gains and Lambda^-1 to Kf (tile pair k at
+// Lf.K + 2 k BT, the space of the stage-wise gains), feed-forward to Sf[Lf.vin + 16 k ..].  false: a pivot was not positive.
+template <typename C>
+MPCQ_COLD bool blk_factor(P<float> Sf, P<float> Kf, P<float> Bk, const Lds& Lf) {
+  constexpr int N = C::N;
+  const int lane = lane_id(), h = lane >> 4, c = lane & 15;
+  const bool vl = c == 14;
+  bool ok = true;
+  float Pop[4], pvl[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) Pop[s] = (4 * h + s == c && c < NX) ? Sf[Lf.wq + VS + c] : 0.0f;
+  for (int k = N / 4 - 1; k >= 0; --k) {
+    const int o = Lf.blk + k * BREC;
+    float Ab[4], Bb[4], FAA[4], Y[4], Lam[4], rhv[4];
+    tl_acc(Bk, o + BK_A, h, c, Ab); tl_acc(Bk, o + BK_B, h, c, Bb);
+    tl_acc(Bk, o + BK_Q, h, c, FAA); tl_acc(Bk, o + BK_S, h, c, Y); tl_acc(Bk, o + BK_R, h, c, Lam);
+    vl_load(Sf + (Lf.rho + 16 * k), h, rhv);
+    const float rtc = Sf[Lf.rt + 16 * k + c];
+    float WA[4] = {0, 0, 0, 0}, WB[4] = {0, 0, 0, 0}, b2[4], Z[4];
+    tl_mm(WA, Pop, Ab);                                   // P Abar (P symmetric: its accumulator form is its row form)
+    tl_mm(WB, Pop, Bb);                                   // P Bbar
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      b2[s] = vl ? pvl[s] : WA[s];                        // column 14 (zero in Abar) carries p
+      Y[s] = vl ? rhv[s] : Y[s];                          // ... and rho
+      Lam[s] += 4 * h + s == c ? rtc : 0.0f;
+      Z[s] = 4 * h + s == c ? 1.0f : 0.0f;
+    }
+    tl_mm(FAA, Ab, b2);                                   // Qbar + Abar^T P Abar | Abar^T p
+    tl_mm(Y, Bb, b2);                                     // M | g = rho + Bbar^T p
+    tl_mm(Lam, Bb, WB);
+    float VY[4] = {0, 0, 0, 0}, VZ[4] = {0, 0, 0, 0};
+    blk_ldl_step<0>(Lam, Y, Z, VY, VZ, h, c, ok); blk_ldl_step<1>(Lam, Y, Z, VY, VZ, h, c, ok);
+    blk_ldl_step<2>(Lam, Y, Z, VY, VZ, h, c, ok); blk_ldl_step<3>(Lam, Y, Z, VY, VZ, h, c, ok);
+    float Kt[4] = {0, 0, 0, 0}, Li[4] = {0, 0, 0, 0}, ZZ[4] = {0, 0, 0, 0};
+    tl_mm(Kt, Z, VY); tl_mm(Li, Z, VZ); tl_mm(ZZ, Y, VY);
+    float kff[4], Ks[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      kff[s] = -Kt[s]; Ks[s] = c < NX ? -Kt[s] : 0.0f;
+      const float pn = FAA[s] - ZZ[s];
+      Pop[s] = (4 * h + s < NX && c < NX) ? pn : 0.0f;
+      pvl[s] = 4 * h + s < NX ? pn : 0.0f;
+    }
+    tl_acc_st(Kf, Lf.K + 2 * k * BT, h, c, Ks);
+    tl_acc_st(Kf, Lf.K + 2 * k * BT + BT, h, c, Li);
+    if (vl) vl_store(Sf + (Lf.vin + 16 * k), h, kff);
+  }
+  __syncthreads();
+  return wave_min<int>(ok ? 1 : 0) != 0;
+}
+
+// forward block sweep: x_0 = 0 ; u_k = K_k x_k + k_k (to Sf[dzo + 16 k ..]) ; x_{k+1} = Abar x_k + Bbar u_k
+template <typename C>
+MPCQ_COLD void blk_forward(P<float> Sf, P<float> Kf, P<float> Bk, const Lds& Lf, const int dzo) {
+  constexpr int N = C::N;
+  const int lane = lane_id(), h = lane >> 4, c = lane & 15;
+  float xc = 0;
+#pragma unroll
+  for (int k = 0; k < N / 4; ++k) {
+    const int o = Lf.blk + k * BREC;
+    float Kr[4], Ar[4], Br[4], xv[4], uv[4];
+    tl_row(Kf, Lf.K + 2 * k * BT, h, c, Kr);
+    const float kf = Sf[Lf.vin + 16 * k + c];
+    l2g<float>(xc, h, xv);
+    const float u = hsum(dot4(Kr, xv)) + kf;
+    if (lane < 16) Sf[dzo + 16 * k + lane] = u;
+    if (k == N / 4 - 1) break;
+    tl_row(Bk, o + BK_A, h, c, Ar); tl_row(Bk, o + BK_B, h, c, Br);
+    l2g<float>(u, h, uv);
+    xc = hsum(dot4(Ar, xv) + dot4(Br, uv));
+  }
+  __syncthreads();
+}
+
+// backward vector sweep for the linear term Sf[Lf.rho]: g = rho + Bbar^T p ; k = -Lambda^-1 g (to Sf[Lf.vin + 16 k ..]) ; p = Abar^T p + K^T g
+template <typename C>
+MPCQ_COLD void blk_backward_vec(P<float> Sf, P<float> Kf, P<float> Bk, const Lds& Lf) {
+  constexpr int N = C::N;
+  const int lane = lane_id(), h = lane >> 4, c = lane & 15;
+  float pc = 0;
+#pragma unroll
+  for (int k = N / 4 - 1; k >= 0; --k) {
+    const int o = Lf.blk + k * BREC;
+    float Bt[4], At[4], Kt[4], Lr[4], pv[4], gv[4];
+    tl_acc(Bk, o + BK_B, h, c, Bt);
+    tl_row(Kf, Lf.K + 2 * k * BT + BT, h, c, Lr);
+    const float rho = Sf[Lf.rho + 16 * k + c];
+    l2g<float>(pc, h, pv);
+    const float g = hsum(dot4(Bt, pv)) + rho;
+    l2g<float>(g, h, gv);
+    const float kf = -hsum(dot4(Lr, gv));
+    if (lane < 16) Sf[Lf.vin + 16 * k + lane] = kf;
+    if (k == 0) break;
+    tl_acc(Bk, o + BK_A, h, c, At); tl_acc(Kf, Lf.K + 2 * k * BT, h, c, Kt);
+    pc = hsum(dot4(At, pv) + dot4(Kt, gv));
+  }
+  __syncthreads();
+}
+
 #ifdef MPCQ_DUMP_AT
 template <typename TQ, typename PT> __device__ inline void dbg_dump(const DevModel<TQ>& m, int slot, PT base, int off, int n) {
   if (!m.dbg) return;
@@ -1518,8 +1761,10 @@ template <typename TQ, typename PT> __device__ inline void dbg_dump(const DevMod
 // the residual of the float solve piles up in it (which is why it was re-swept every iteration until round 5) -- but all the mixed-precision
 // method needs from the interior point is the working set, which it then checks against double residuals: one sweep of four less per
 // iteration, +2 % on the lockstep rate, the soaks as clean as before.
-template <typename C, typename TQ = typename C::T, bool GAB = C::GAB, typename M = DevModel<TQ>, typename PA = P<TQ>>
-MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, const TQ tol, const TQ gm, int& it PF_ARG, const TQ rd_floor = TQ(3e-4), const int cap = 0) {
+// BLK: the Newton systems on the four-stage blocks (blk_factor and its sweeps; float only, block records at L.blk of Bk)
+template <typename C, typename TQ = typename C::T, bool GAB = C::GAB, typename M = DevModel<TQ>, typename PA = P<TQ>, bool BLK = false>
+MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, const TQ tol, const TQ gm, int& it PF_ARG, const TQ rd_floor = TQ(3e-4), const int cap = 0,
+                           P<TQ> Bk = P<TQ>(nullptr)) {
   constexpr int N = C::N > 0 ? C::N : 1, nv = N * NU, R = (nv + 63) / 64;
   const int tid = lane_id();
   int status = 2;
@@ -1561,11 +1806,16 @@ MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, co
     }
     __syncthreads();
     PF_START();
-    const bool fok = riccati_factor<C, false, false, TQ, GAB>(m, S, A, Kb, L PF_PASS, (TQ*)nullptr, P<TQ>(nullptr), P<TQ>(nullptr), -1, true);
+    bool fok;
+    if constexpr (BLK) fok = blk_factor<C>(S, Kb, Bk, L);
+    else fok = riccati_factor<C, false, false, TQ, GAB>(m, S, A, Kb, L PF_PASS, (TQ*)nullptr, P<TQ>(nullptr), P<TQ>(nullptr), -1, true);
     PF_STOP(PF_FACTOR);
     if (it == 0) { DBG_DUMP(2, 0, S, L.rt, nv); DBG_DUMP(2, 128, Kb, L.K, N * KS); DBG_DUMP(2, 2048, Kb, L.Linv, N * 16); DBG_DUMP(2, 3000, S, L.vin, N * VS); }
     if (!fok) { status = 4; break; }
-    PF_START(); riccati_forward<C, false, TQ, GAB>(m, S, A, Kb, L, L.dza PF_PASS); PF_STOP(PF_FWD);
+    PF_START();
+    if constexpr (BLK) blk_forward<C>(S, Kb, Bk, L, L.dza);
+    else riccati_forward<C, false, TQ, GAB>(m, S, A, Kb, L, L.dza PF_PASS);
+    PF_STOP(PF_FWD);
     if (it == 0) { DBG_DUMP(3, 0, S, L.dza, nv); DBG_DUMP(3, 128, S, L.Dx, (N + 1) * VS); }
     // step lengths without divisions: alpha = 1 / max_i(-ds_i / s_i); every quotient is a product with a reciprocal
     TQ da[R], dla[R], dua[R], rll[R], rlu[R], ainv = 1;
@@ -1598,9 +1848,15 @@ MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, co
       if (on[r]) S[L.rho + ix[r]] = rho[r];
     }
     __syncthreads();
-    PF_START(); riccati_backward_vec<C, TQ, GAB>(m, S, A, Kb, L, false); PF_STOP(PF_BWD);
+    PF_START();
+    if constexpr (BLK) blk_backward_vec<C>(S, Kb, Bk, L);
+    else riccati_backward_vec<C, TQ, GAB>(m, S, A, Kb, L, false);
+    PF_STOP(PF_BWD);
     if (it == 0) { DBG_DUMP(4, 0, S, L.rho, nv); DBG_DUMP(4, 128, S, L.vin, N * VS); }
-    PF_START(); riccati_forward<C, false, TQ, GAB>(m, S, A, Kb, L, L.dz PF_PASS); PF_STOP(PF_FWD);
+    PF_START();
+    if constexpr (BLK) blk_forward<C>(S, Kb, Bk, L, L.dz);
+    else riccati_forward<C, false, TQ, GAB>(m, S, A, Kb, L, L.dz PF_PASS);
+    PF_STOP(PF_FWD);
     if (it == 0) { DBG_DUMP(5, 0, S, L.dz, nv); DBG_DUMP(5, 128, S, L.Dx, (N + 1) * VS); }
     TQ d[R], dl[R], du[R], apinv = 1, adinv = 1;
 #pragma unroll
@@ -1630,7 +1886,8 @@ MPCQ_COLD int ipm_run_regs(const M& m, P<TQ> S, PA A, P<TQ> Kb, const Lds& L, co
         S[L.grad + gi[r]] = g[r];
       }
     }
-    for (int i = tid; i < (N + 1) * VS; i += 64) S[L.dx + i] += ap * S[L.Dx + i];
+    if constexpr (!BLK)   // (the block sweeps produce no state trajectory: in the float stage it is bookkeeping nobody reads)
+      for (int i = tid; i < (N + 1) * VS; i += 64) S[L.dx + i] += ap * S[L.Dx + i];
     __syncthreads();
   }
   return status;
@@ -1955,7 +2212,6 @@ MPCQ_PHASE bool polish(const DevModel<TQ>& m, P<TQ> S, P<TQ> A, P<TQ> G, const L
 #if defined(MPCQ_PROFILE) && !defined(MPCQ_PROFILE_FWD) && !defined(MPCQ_PROFILE_FAC) && !defined(MPCQ_PROFILE_SERIAL) && !defined(MPCQ_PROFILE_OTHER)
     pf.acc[11] += nblk;                        // inputs pinned
     pf.acc[12] += any_release ? 1 : 0;         // passes with a release
-    pf.acc[15] += (any_release && nblk > 0) ? 1 : 0;   // passes with both
 #endif
     if (feasible && !any_release) { settled = true; passes += 1; break; }
     // a bulk release that bounces back wholesale with most of the inputs saturated: far from the optimal working set,
@@ -2544,14 +2800,14 @@ MPCQ_PHASE bool polish_mixed(const DevModel<float>& m, P<double> D, P<float> S, 
 #define MPCQ_HYBRID_MAXIT 24   // stalls on the same QPs -- hands over what it has: the active-set method verifies what it ends on itself)
 #endif
 template <typename C, bool GAB = C::GAB>
-MPCQ_COLD int ipm_float_stage(const DevModel<double>& m, P<double> S, P<double> A, P<double> Kb, const Lds& L, const double gm, int& it PF_ARG) {
+MPCQ_COLD int ipm_float_stage(const DevModel<double>& m, P<double> S, P<double> A, P<double> Kb, P<double> G, const Lds& L, const double gm, int& it PF_ARG) {
   constexpr int N = C::N, nv = N * NU, R = (nv + 63) / 64, RG = (N * VS + 63) / 64;
   const int tid = lane_id();
   Lds Lf = L;   // stage records: the double ones (offsets into A unchanged); QP workspace and gains: the float view
   Lf.z = 2 * L.z; Lf.sl = 2 * L.sl; Lf.su = 2 * L.su; Lf.ll = 2 * L.ll; Lf.lu = 2 * L.lu; Lf.dza = 2 * L.dza; Lf.dz = 2 * L.dz;
   Lf.rho = 2 * L.rho; Lf.act = 2 * L.act; Lf.rt = 2 * L.rt; Lf.grad = 2 * L.grad; Lf.vin = 2 * L.vin; Lf.dx = 2 * L.dx; Lf.Dx = 2 * L.Dx;
-  Lf.K = 2 * L.K; Lf.Linv = 2 * L.Linv; Lf.sF = 2 * L.sF; Lf.sT = 2 * L.sT; Lf.stv = 2 * L.stv; Lf.wq = 2 * L.wq;
-  const P<float> Sf = as_float(S), Kf = as_float(Kb);
+  Lf.K = 2 * L.K; Lf.Linv = 2 * L.Linv; Lf.sF = 2 * L.sF; Lf.sT = 2 * L.sT; Lf.stv = 2 * L.stv; Lf.wq = 2 * L.wq; Lf.blk = 2 * L.blk;
+  const P<float> Sf = as_float(S), Kf = as_float(Kb), Gf = as_float(G);
   // the start, read in double and rounded behind a barrier (a float array overlaps the double elements of other lanes)
   double zr[R], slr[R], sur[R], llr[R], lur[R], gr[RG];
 #pragma unroll
@@ -2575,7 +2831,11 @@ MPCQ_COLD int ipm_float_stage(const DevModel<double>& m, P<double> S, P<double> 
   for (int i = tid; i < (N + 1) * VS; i += 64) Sf[Lf.dx + i] = 0;   // (the float state trajectory is bookkeeping nobody reads)
   __syncthreads();
   int itf = 0;
-  const int stf = ipm_run_regs<C, float, GAB>(m, Sf, A, Kf, Lf, MPCQ_HYBRID_TOL, (float)gm, itf PF_PASS, MPCQ_HYBRID_RD, MPCQ_HYBRID_MAXIT);
+  int stf;
+  if constexpr (blk_ipm<C>()) {
+    PF_START(); blk_form<C>(Sf, A, Gf, L, Lf); PF_STOP(PF_FORM);
+    stf = ipm_run_regs<C, float, GAB, DevModel<double>, P<double>, true>(m, Sf, A, Kf, Lf, MPCQ_HYBRID_TOL, (float)gm, itf PF_PASS, MPCQ_HYBRID_RD, MPCQ_HYBRID_MAXIT, Gf);
+  } else stf = ipm_run_regs<C, float, GAB>(m, Sf, A, Kf, Lf, MPCQ_HYBRID_TOL, (float)gm, itf PF_PASS, MPCQ_HYBRID_RD, MPCQ_HYBRID_MAXIT);
   it += itf;
   // back to double: the smaller slack of an input is taken as it is, the point and the other slack follow from it (both positive, and
   // consistent with the bounds to double rounding -- what a continuation in double needs)
@@ -2657,7 +2917,7 @@ MPCQ_PHASE int solve_qp(const DevModel<TQ>& m, P<double> D, P<TQ> S, P<TQ> A, P<
   int fit = 0;   // interior-point iterations executed in float (reported in the work word: what a latency model prices with the float chains)
   if constexpr (MPCQ_HYBRID_IPM != 0 && C::N > 0 && C::N * NU <= 128) {
     if (m.polish_max > 0) {
-      const int stf = ipm_float_stage<C>(m, S, A, Kb, L, gm, it PF_PASS);
+      const int stf = ipm_float_stage<C>(m, S, A, Kb, G, L, gm, it PF_PASS);
       fit = it;                        // (the interior point's iterations so far are the float ones)
       handed = stf == 0 || stf == 2;   // (2: stalled short of its tolerance at its iteration cap -- the working set it indicates is tried all the same)
       if (!handed) { broke = true; interior_start(); }

@@ -58,7 +58,8 @@ def main():
     if mean[14] > 0 and os.environ.get("PROF_MODE") not in ("fac", "serial", "other"):   # active-set statistics of the fp64 path (diagnostic counters of polish())
         tot = acc.sum(axis=0)
         print(f"factorisations per quad-step {mean[14]:.3f} (slowest quad of a launch: {mxs[14]:.2f}); stages visited per factorisation {tot[13] / tot[14]:.1f}; "
-              f"pins per quad-step {mean[11]:.3f}, passes with a release {mean[12]:.3f}, with both {mean[15]:.3f}")
+              f"pins per quad-step {mean[11]:.3f}, passes with a release {mean[12]:.3f}")
+        print(f"{'blk_form':10s} {mean[15]:12.0f} {100 * mean[15] / mean[10]:6.1f}% {mxs[15]:20.0f}   (block formation of the float interior point, once per fallback solve)")
     other = mean[10] - mean[:10].sum()
     print(f"{'other':10s} {other:12.0f} {100 * other / mean[10]:6.1f}%")
 
